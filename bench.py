@@ -1,6 +1,7 @@
 """bench.py -- protein-pairs/sec (fwd+bwd) of one IEGMN stack on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload B|A|C|D|E|R] [--dtype f32|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload B|A|C|D|E|R] [--dtype f32|bf16] [--full]
+                    [--dump-outputs DIR]
 
 A "step" = zero grads -> Rigid_Body_Docking_Net forward -> fixed scalar loss
 -> backward, on one synthetic batch that is already resident in HBM (the slice
@@ -16,7 +17,13 @@ The default workload is B for every N, so that the driver's N = 1, 2, 4, 8 runs 
 residues; synthetic.realistic_sizes), which also reports residue-pairs/s (sum n_lig * n_rec per second: the quadratic
 attention term) and the size spread.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields (metric,
+value, unit, higher_is_better, dtype, ms_per_step, ...), the configuration and "whole_step".  With --dump-outputs DIR
+it also writes what the last timed step computed (loss, lig, Yl, Yr, T, b and the flat parameter gradient) as
+DIR/<name>.npy in float32 / float64; inputs and weights are seeded, so two builds can be compared output for output.
+
+With --full the run also checks the fused scalar loss against its torch formulation, times the all-reduce alone under
+a process group and adds
   "roofline":      the dominant kernel (edge-message backward/forward), measured live with HIP events on the launch
                    stream: algorithmic FLOPs|bytes per launch / avg duration of batched standalone launches;
   "roofline_all":  every kernel family >= 3 % of the step, timed inside an eager step with the library's launch
@@ -26,7 +33,8 @@ Rank 0 prints ONE JSON line with the contract fields plus
                    its one-thread and one-pair-per-step variants (N=1 only; the only place `oracle` is imported);
   "secondary":     (default workload B only) the other BASELINE.json configs timed the same way with 3 + 10 steps:
                    C in bf16 (configs[2]), E (configs[4]) and the ragged workload R on one GPU; D (configs[3]: 64 x (300,300)
-                   per GPU in bf16, RCCL all-reduce inside the step graph) when launched by torch.distributed.run.
+                   per GPU in bf16, RCCL all-reduce inside the step graph) when launched by torch.distributed.run;
+  "inference":     (default workload B, one GPU) the forward alone of the same batch, replayed from its own hipGraph.
 """
 import argparse
 import ctypes as C
@@ -598,10 +606,12 @@ class _Run:
 
 
 def run_workload(workload, dtype, steps, warmup, dev, rank, world, use_dist, backend, dropout=0.0, dropout_masks='library',
-                 eager=False, time_allreduce=True):
+                 eager=False, time_allreduce=True, check_loss=True, keep_outputs=False):
     """Build the model + the synthetic batch of `workload`, capture zero-grad -> forward -> loss -> backward (+ the RCCL
     all-reduce under a process group) into a hipGraph, run `warmup` untimed and `steps` timed steps bracketed by
-    barrier + synchronize, max over ranks.  Returns a _Run (seconds for the timed steps in .dt)."""
+    barrier + synchronize, max over ranks.  Returns a _Run (seconds for the timed steps in .dt).  `check_loss`: compare
+    the fused scalar loss with its torch formulation first; `keep_outputs`: copy what the last timed step computed to the
+    host (R.outputs, before the all-reduce is timed alone)."""
     import torch.distributed as dist
     from equidock_public_amd import config, graph, model, parallel, synthetic
     from equidock_public_amd import losses
@@ -627,6 +637,7 @@ def run_workload(workload, dtype, steps, warmup, dev, rank, world, use_dist, bac
     lig_w = torch.cat([torch.full((n, 1), 1.0 / (3 * n)) for n in packed.lig_counts]).to(dev)
     reducer = parallel.FlatGradAllReduce(net)
     scalar_loss = losses.ScalarLoss(packed, args_model['num_att_heads'])
+    last = {}       # the tensors of the latest compute() (under graph replay: the captured ones, rewritten every replay)
 
     def compute():
         # zero grads -> forward -> fixed scalar loss (value + its gradient w.r.t. the outputs: ONE launch, eqd_scalar_loss)
@@ -635,6 +646,7 @@ def run_workload(workload, dtype, steps, warmup, dev, rank, world, use_dist, bac
         lig, Yl, Yr, T, b = net.forward_batched(g)
         loss, grads = scalar_loss(lig, Yl, Yr)
         torch.autograd.backward([lig, Yl, Yr], list(grads))
+        last.update(loss=loss, lig=lig, Yl=Yl, Yr=Yr, T=T, b=b)
         return loss
 
     def compute_torch_loss():      # the same step with the loss written in torch ops (cross-check of the fused kernel)
@@ -643,13 +655,16 @@ def run_workload(workload, dtype, steps, warmup, dev, rank, world, use_dist, bac
         loss = batched_loss(lig, Yl, Yr, lig_w)
         loss.backward()
         return loss
-    torch.manual_seed(4242)     # (same dropout masks in both evaluations)
-    l_ref = float(compute_torch_loss().detach())
-    g_ref = reducer.flat.clone()
-    torch.manual_seed(4242)
-    l_got = float(compute())
-    if abs(l_got - l_ref) > 1e-5 * abs(l_ref) or float((reducer.flat - g_ref).abs().max()) > 1e-5 * float(g_ref.abs().max()):
-        raise SystemExit(f"fused scalar loss disagrees with its torch formulation: {l_got} vs {l_ref}")
+    if check_loss:
+        torch.manual_seed(4242)     # (same dropout masks in both evaluations)
+        l_ref = float(compute_torch_loss().detach())
+        g_ref = reducer.flat.clone()
+        torch.manual_seed(4242)
+        l_got = float(compute())
+        if abs(l_got - l_ref) > 1e-5 * abs(l_ref) or float((reducer.flat - g_ref).abs().max()) > 1e-5 * float(g_ref.abs().max()):
+            raise SystemExit(f"fused scalar loss disagrees with its torch formulation: {l_got} vs {l_ref}")
+    else:
+        torch.manual_seed(4242)     # (the same dropout masks from run to run)
 
     # Default: capture zero-grad -> forward -> loss -> backward ONCE into a hipGraph and replay it every step (every
     # kernel still runs every step).  With a process group the RCCL all-reduce of the flat gradient is captured INSIDE the
@@ -717,6 +732,10 @@ def run_workload(workload, dtype, steps, warmup, dev, rank, world, use_dist, bac
     if use_dist:
         dist.barrier()
     dt = time.perf_counter() - t0
+    outputs = None
+    if keep_outputs:
+        outputs = {k: v.detach().cpu() for k, v in last.items()}
+        outputs['grad_flat'] = reducer.flat.detach().cpu()
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -749,7 +768,29 @@ def run_workload(workload, dtype, steps, warmup, dev, rank, world, use_dist, bac
     R.dt, R.host_dt, R.loss, R.steps, R.warmup = dt, host_dt, float(loss.detach()), steps, warmup
     R.graph_mode, R.allreduce_in_graph, R.allreduce_us = graph_mode, allreduce_in_graph, allreduce_us
     R.launches = None
+    R.outputs = outputs
     return R
+
+
+DUMP_MAX_ELEMS = 2 * 1024 * 1024       # per array (8 MB as float32): seven arrays stay under 64 MB in all
+
+
+def dump_outputs(outputs, out_dir):
+    """DIR/<name>.npy for every output of the last timed step: float64 stays float64, everything else becomes float32.
+    An array larger than DUMP_MAX_ELEMS is replaced by a fixed, seeded sample of its flattened elements (sorted
+    indices), the same sample in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in sorted(outputs.items()):
+        a = t.double().numpy() if t.dtype == torch.float64 else t.float().numpy()
+        a = np.ascontiguousarray(a)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def time_inference(net, g, ppg, dev, steps=30, warmup=5):
@@ -908,7 +949,7 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--workload', default=None, choices=sorted(WORKLOADS),
-                    help="default B (BASELINE.json configs[1]) WITH the \"secondary\" / \"inference\" blocks; an explicitly "
+                    help="default B (BASELINE.json configs[1]), with --full also the \"secondary\" / \"inference\" blocks; an explicitly "
                          "named workload (also `--workload B`) runs that workload alone, so that a profiler around the "
                          "command sees one workload's kernels only")
     ap.add_argument('--dtype', default=None, choices=('f32', 'bf16'),
@@ -926,10 +967,17 @@ def main():
                     help="run ONLY the reference's training step (model + MSE / pocket-OT / intersection losses + backward: "
                          "train_step.TrainStep, three hipGraphs around the exact-OT host solve) on the named workload and print its "
                          "block - what a profiler should wrap to see the gap the host solve leaves on the GPU timeline")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help="besides the headline line: the fused-loss cross-check, the all-reduce timed alone, the roofline / "
+                         "step-profile / counter blocks, the CPU baseline and (default workload) the secondary and inference "
+                         "blocks; a plain run measures the timed steps only")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps write what the last step computed (loss, lig, Yl, Yr, T, b, grad_flat) as "
+                         "DIR/<name>.npy (float32 / float64; arrays above 2M elements as a fixed seeded sample)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(with --full) leave out the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='(with --full) leave out the roofline / step-profile blocks')
     ap.add_argument('--no-secondary', action='store_true',
-                    help="skip the \"secondary\" block of the default (workload B) line: short timed runs of the other BASELINE "
+                    help="(with --full) skip the \"secondary\" block of the default (workload B) line: short timed runs of the other BASELINE "
                          "configs - C in bf16 (configs[2]), E (configs[4]) and the ragged workload R on one GPU; D (configs[3], "
                          "64 x (300,300) per GPU in bf16 with the RCCL all-reduce) under torch.distributed.run")
     ap.add_argument('--eager', action='store_true', help='launch every kernel of every step from the host instead of replaying a captured hipGraph of the step (zero-grad, forward, loss, backward; the gradient all-reduce always runs outside the graph).  Same kernels either way; the replay takes the host (torch autograd + the launches, 0.7-1.5 ms depending on the box) off the critical path of a 1.5 ms step')
@@ -939,6 +987,10 @@ def main():
         a.no_secondary = True
     else:
         a.workload = 'B'
+    if not a.full:      # a plain run: the timed steps and the headline line only
+        a.no_secondary = a.no_roofline = a.no_cpu_baseline = True
+    if a.dump_outputs and a.train_step:
+        ap.error('--dump-outputs writes the model step\'s outputs; it does not apply to --train-step')
 
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
@@ -988,7 +1040,11 @@ def main():
             dist.init_process_group(backend)
 
     R = run_workload(a.workload, a.dtype, a.steps, a.warmup, dev, rank, world, use_dist, backend, dropout=a.dropout,
-                     dropout_masks=a.dropout_masks, eager=a.eager)
+                     dropout_masks=a.dropout_masks, eager=a.eager, time_allreduce=a.full, check_loss=a.full,
+                     keep_outputs=bool(a.dump_outputs) and rank == 0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(R.outputs, a.dump_outputs)
+        R.outputs = None
     if a.train_step:
         blk = time_train_step(R, dev, world, use_dist, backend, steps=a.steps, warmup=a.warmup,
                               eager_tail=os.environ.get('EQD_BENCH_TRAIN_EAGER_TAIL', '1') != '0')

@@ -1,7 +1,7 @@
 # Round-6 measurement driver (runs on the GPU box through gpurun; writes under gpurun_out/).
 #   bash profiles/measure_r06.sh TAG step [step ...]
 # steps:  tests | testsfast | testsbig | test:<pytest -k expression>
-#         bench:<W>[:bf16][:full]     bench.py line of workload W (":full" keeps the CPU baseline and the roofline part)
+#         bench:<W>[:bf16][:full]     bench.py line of workload W (":full" = bench.py --full: the CPU baseline and the roofline part)
 #         eager:<W>[:bf16]            the same line with --eager
 #         drop:<W>[:bf16][:torchpack|:lib]  the line with --dropout 0.25 (training-mode masks drawn every step;
 #                                     lib = --dropout-masks library, torchpack = mask packing in torch operators)
@@ -25,7 +25,7 @@ for what in "$@"; do
   DT=""; SUF=""; FULL="--no-cpu-baseline --no-roofline"
   for o in "$opt1" "$opt2"; do
     [ "$o" = "bf16" ] && DT="--dtype bf16" && SUF="_bf16"
-    [ "$o" = "full" ] && FULL=""
+    [ "$o" = "full" ] && FULL="--full"
   done
   ST="--steps 20 --warmup 5"; [ "$W" = "B" ] && ST=""; [ "$W" = "A" ] && ST=""
   case $cmd in
@@ -94,8 +94,8 @@ for what in "$@"; do
         python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$W$SUF $AB_VAR=$val', d['value'], 'pairs/s', d['ms_per_step'], 'ms')" >> $O/${TAG}_ab.txt 2>&1
     done; done ;;
   dprehearsal)   # the driver's N > 1 launch line with one rank on RCCL (world of one)
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/${TAG}_bench_rccl1_B.log 2>&1
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --workload D --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $O/${TAG}_bench_rccl1_D.log 2>&1 ;;
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-roofline > $O/${TAG}_bench_rccl1_B.log 2>&1
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --workload D --steps 10 --warmup 3 --full --no-cpu-baseline --no-roofline > $O/${TAG}_bench_rccl1_D.log 2>&1 ;;
   collate)
     python profiles/bench_collate.py > $O/${TAG}_collate.txt 2>&1 ;;
   frows)

@@ -552,7 +552,7 @@ def test_bench_workload_d_on_rccl_world_of_one(dev):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', '29541', os.path.join(root, 'bench.py'), '--gpus', '1', '--workload', 'D', '--steps', '3',
-           '--warmup', '2', '--no-cpu-baseline', '--no-roofline']
+           '--warmup', '2', '--full', '--no-cpu-baseline', '--no-roofline']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
@@ -578,8 +578,8 @@ def test_bench_gpus2_plain_command_two_ranks_on_one_gpu(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY='0', EQD_BENCH_ONE_DEVICE='1', EQD_BENCH_BACKEND='gloo')
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-           '--no-roofline', '--no-secondary']
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full',
+           '--no-cpu-baseline', '--no-roofline', '--no-secondary']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
