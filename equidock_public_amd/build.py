@@ -1,4 +1,5 @@
-"""Build libequidock_hip.so (gfx950) in-tree with hipcc.  No GPU is needed to compile."""
+"""Build libequidock_hip.so and libequidock_dock.so (gfx950) in-tree with hipcc, and libequidock_host.so with g++.  No GPU
+is needed to compile."""
 import glob
 import os
 import subprocess
@@ -45,6 +46,7 @@ def build(force=False, verbose=True):
     if force or jobs or _stale(LIB, objs):
         run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs)
     build_host(force, verbose)
+    build_dock(force, verbose)
     return LIB
 
 
@@ -76,6 +78,27 @@ def build_host(force=False, verbose=True):
         if r.returncode != 0:
             raise RuntimeError(f"g++ failed:\n{r.stdout}\n{r.stderr}")
     return HOST_LIB
+
+
+DOCK_LIB = os.path.join(HERE, 'libequidock_dock.so')
+
+
+def build_dock(force=False, verbose=True):
+    """libequidock_dock.so: batched inference post-processing (csrc_dock/, include/equidock_dock.h).  It includes the
+    reduction helpers of csrc/eqd_common.h; its symbols are hidden except the eqd_dock_* entry points."""
+    srcs = sorted(glob.glob(os.path.join(HERE, 'csrc_dock', '*.hip')))
+    inc = os.path.join(os.path.dirname(HERE), 'include')
+    deps = srcs + [os.path.join(CSRC, 'eqd_common.h'), os.path.join(inc, 'equidock_hip.h'), os.path.join(inc, 'equidock_dock.h')]
+    if force or _stale(DOCK_LIB, deps):
+        cmd = [HIPCC] + FLAGS + ['-fvisibility=hidden', '-shared', '-o', DOCK_LIB] + srcs
+        if verbose:
+            print(' '.join(cmd), flush=True)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{r.stdout}\n{r.stderr}")
+        if verbose and r.stderr.strip():
+            print(r.stderr, file=sys.stderr)
+    return DOCK_LIB
 
 
 if __name__ == '__main__':

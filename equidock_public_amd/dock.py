@@ -1,0 +1,325 @@
+"""Batched docking inference: src/inference_rigid.py's loop over a directory of complexes (:85-245) for N complexes at once.
+
+    graphs (per complex, device)  ->  one batched eval forward per chunk  ->  apply_rigid to each ligand's atoms
+    ->  remove_clashes_batch: clash removal of ALL complexes in one device loop (libequidock_dock.so), each stopping on
+        its own  ->  PDB files and, with ground truth, the CRMSD / IRMSD summary
+
+`remove_clashes_batch` is `inference.remove_clashes` for a list of complexes: same keys, same stop rule, same meaning;
+`dock_complexes` is the Python API, `python -m equidock_public_amd.dock` the command-line counterpart of
+inference_rigid.py.  There is no fallback: a missing libequidock_dock.so is an error.
+"""
+import argparse
+import ctypes as C
+import glob
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+from . import _lib, config, featurize as FZ, graph as G, inference as INF
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+DOCK_LIB_PATH = os.path.join(HERE, 'libequidock_dock.so')
+DOCK_ABI_VERSION = 1
+
+_dock = None
+_dock_is_sim = False
+
+
+def _declare(lib):
+    lib.eqd_dock_abi_version.restype = C.c_int
+    lib.eqd_dock_last_error.restype = C.c_char_p
+    lib.eqd_dock_is_simulator.restype = C.c_int
+    lib.eqd_dock_clash_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_clash_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    lib.eqd_dock_clash_init.restype = C.c_int
+    lib.eqd_dock_clash_init.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]
+    lib.eqd_dock_clash_iterations.restype = C.c_int
+    lib.eqd_dock_clash_iterations.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                              C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p]
+
+
+def _bind(path):
+    global _dock, _dock_is_sim
+    lib = C.CDLL(path)
+    _declare(lib)
+    if lib.eqd_dock_abi_version() != DOCK_ABI_VERSION:
+        raise _lib.EquidockHipError(f"{path}: dock ABI version {lib.eqd_dock_abi_version()} != {DOCK_ABI_VERSION}")
+    _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
+    return lib
+
+
+def load_dock_library():
+    """Load libequidock_dock.so built by equidock_public_amd/build.py.  Raises if it is missing."""
+    if _dock is not None:
+        return _dock
+    if not os.path.exists(DOCK_LIB_PATH):
+        raise _lib.EquidockHipError(f"{DOCK_LIB_PATH} is missing: build it with `python -m equidock_public_amd.build` "
+                                    "(hipcc, gfx950).  There is no CPU fallback for batched clash removal.")
+    return _bind(DOCK_LIB_PATH)
+
+
+def load_dock_library_for_testing(path):
+    """TESTS ONLY: bind an explicitly given build of the dock ABI (the x86 simulator build of csrc_dock/)."""
+    return _bind(path)
+
+
+def unload_dock_for_testing():
+    global _dock, _dock_is_sim
+    _dock, _dock_is_sim = None, False
+
+
+def check(rc):
+    if rc != 0:
+        raise _lib.EquidockHipError(f"libequidock_dock error {rc}: {_dock.eqd_dock_last_error().decode()}")
+
+
+def _require_device(t, what):
+    if _dock_is_sim:
+        if t.is_cuda:
+            raise _lib.EquidockHipError(f"{what}: the host simulator only takes CPU tensors")
+    elif not t.is_cuda:
+        raise _lib.EquidockHipError(f"{what} is on {t.device}: batched clash removal runs only on an MI355X through "
+                                    "libequidock_dock.so (no CPU fallback)")
+    return t
+
+
+def _stream(dev):
+    return C.c_void_p(0) if _dock_is_sim else C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _offsets(sizes):
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(sizes)
+    if off[-1] > np.iinfo(np.int32).max:
+        raise ValueError(f"{int(off[-1])} atoms do not fit int32 offsets: split the batch")
+    return np.ascontiguousarray(off.astype(np.int32))
+
+
+def remove_clashes_batch(ligand_atoms_list, receptor_atoms_list, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000,
+                         check_every=50):
+    """inference.remove_clashes for C complexes in one device loop.  ligand_atoms_list[c] [n_c, 3]: the docked ligand of
+    complex c (all atoms, after apply_rigid); receptor_atoms_list[c] [m_c, 3].  `max_it`: an int or one per complex.
+    Returns one dict per complex with the keys and meaning of remove_clashes (positions, euler, translation, iterations,
+    loss).  The host reads the 4-byte completion counter every `check_every` iterations."""
+    lib = load_dock_library()
+    ligs, recs = list(ligand_atoms_list), list(receptor_atoms_list)
+    if len(ligs) != len(recs):
+        raise ValueError(f"{len(ligs)} ligands for {len(recs)} receptors")
+    n = len(ligs)
+    if n == 0:
+        return []
+    caps = [int(max_it)] * n if np.ndim(max_it) == 0 else [int(v) for v in max_it]
+    if len(caps) != n:
+        raise ValueError(f"{len(caps)} max_it values for {n} complexes")
+    if int(check_every) < 1:
+        raise ValueError(f"check_every = {check_every}")
+    ligs = [_require_device(x.detach().to(torch.float32).reshape(-1, 3).contiguous(), f'ligand atoms {i}') for i, x in enumerate(ligs)]
+    recs = [_require_device(x.detach().to(torch.float32).reshape(-1, 3).contiguous(), f'receptor atoms {i}') for i, x in enumerate(recs)]
+    dev = ligs[0].device
+    lig_off, rec_off = _offsets([x.shape[0] for x in ligs]), _offsets([x.shape[0] for x in recs])
+    caps_np = np.ascontiguousarray(np.asarray(caps, dtype=np.int32))
+    lo, ro = lig_off.ctypes.data_as(C.c_void_p), rec_off.ctypes.data_as(C.c_void_p)
+    wsb = lib.eqd_dock_clash_workspace_bytes(n, lo, ro)
+    if wsb == 0:
+        check(2)
+    lig_cat, rec_cat = torch.cat(ligs, 0), torch.cat(recs, 0)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    states = torch.empty(n * C.sizeof(INF.EqdClashState), dtype=torch.uint8, device=dev)
+    n_done = torch.empty(1, dtype=torch.int32, device=dev)
+    st = _stream(dev)
+    with _lib.device_guard(dev):
+        check(lib.eqd_dock_clash_init(n, lo, ro, caps_np.ctypes.data_as(C.c_void_p), _lib.ptr(states), _lib.ptr(n_done),
+                                      _lib.ptr(ws), C.c_size_t(wsb), st))
+        issued, bound = 0, max(max(caps), 0) + 1      # every complex has finished after max(max_it) + 1 iterations
+        while True:
+            n_iter = min(int(check_every), bound - issued)
+            issued += n_iter
+            check(lib.eqd_dock_clash_iterations(n_iter, n, lo, ro, _lib.ptr(lig_cat), _lib.ptr(rec_cat),
+                                                C.c_float(sigma), C.c_float(surface_ct), C.c_float(loss_stop),
+                                                _lib.ptr(states), _lib.ptr(n_done), _lib.ptr(ws), C.c_size_t(wsb), st))
+            if int(n_done.cpu()[0]) >= n:          # the periodic look at the completion counter
+                break
+            if issued >= bound:
+                raise _lib.EquidockHipError(f"clash removal: {int(n_done.cpu()[0])} of {n} complexes finished after "
+                                            f"{issued} iterations (max_it {max(caps)})")
+    host = (INF.EqdClashState * n).from_buffer_copy(states.cpu().numpy().tobytes())
+    out = []
+    for c in range(n):
+        euler = np.asarray(host[c].euler[:], dtype=np.float32)
+        trans = np.asarray(host[c].trans[:], dtype=np.float32)
+        pos = INF.apply_rigid(INF.get_rot_mat(torch.from_numpy(euler)).to(dev), trans, ligs[c])
+        out.append({'positions': pos, 'euler': euler, 'translation': trans, 'iterations': int(host[c].it),
+                    'loss': float(host[c].loss)})
+    return out
+
+
+# ---- model + files ------------------------------------------------------------------------------------------------
+def load_checkpoint(path, device):
+    """Rigid_Body_Docking_Net from a reference checkpoint {'args', 'state_dict'} (src/inference_rigid.py:97-112): the
+    `args` keys the drop-in reads are taken from the checkpoint, the rest from config.published_args().  The whole
+    checkpoint `args` stays available as `net.checkpoint_args` (graph_cutoff, graph_max_neighbor)."""
+    from .model import Rigid_Body_Docking_Net
+    ckpt = torch.load(path, map_location='cpu', weights_only=False)
+    if not isinstance(ckpt, dict) or 'args' not in ckpt or 'state_dict' not in ckpt:
+        raise ValueError(f"{path}: expected a dict with 'args' and 'state_dict'")
+    device = torch.device(device)
+    base = config.published_args()
+    args = {k: ckpt['args'].get(k, v) for k, v in base.items()}
+    args.update(debug=False, device=device)
+    net = Rigid_Body_Docking_Net(args)
+    net.load_state_dict(ckpt['state_dict'])
+    net = net.to(device).eval()
+    net.checkpoint_args = dict(ckpt['args'])
+    return net
+
+
+def _side(x):
+    """(residues, all ATOM coordinates in file order) of a PDB path or a residue list."""
+    if isinstance(x, (str, os.PathLike)):
+        return FZ.read_pdb_residues(x), INF.read_pdb_atoms(x)
+    return list(x), FZ.atoms_ragged(list(x))[0]
+
+
+def _sync(dev):
+    if dev.type == 'cuda':
+        torch.cuda.synchronize(dev)
+
+
+def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=None, device=None, cutoff=30.0,
+                   max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50):
+    """Dock a list of (ligand, receptor) complexes, each side a PDB path or a list of featurize.Residue (the ligand's
+    file / residues in their input pose, the receptor's in the bound pose - the reference's `*_l_b.pdb` and
+    `*_r_b_COMPLEX.pdb`).  Per chunk of `max_complexes_per_batch` complexes (all at once by default): graphs on the
+    device, one batched eval forward, apply_rigid to every ligand atom, then remove_clashes_batch.
+
+    Returns one dict per complex: rotation [3, 3], translation [3] (numpy), ligand_atoms_docked (apply_rigid of all ligand
+    atoms, before clash removal) and ligand_atoms (after it; the same tensor without clash removal), clash_iterations,
+    clash_loss, n_ligand_atoms / n_receptor_atoms, and `batch_seconds`: wall times of the complex's chunk (graphs, model,
+    rigid, clashes, total; device-synchronised)."""
+    complexes = list(complexes)
+    dev = torch.device(device) if device is not None else next(net.parameters()).device
+    step = len(complexes) if not max_complexes_per_batch else int(max_complexes_per_batch)
+    results = []
+    was_training = net.training
+    net.eval()
+    try:
+        for b0 in range(0, len(complexes), max(step, 1)):
+            chunk = complexes[b0:b0 + step]
+            _sync(dev)
+            t0 = time.perf_counter()
+            pairs, lig_atoms, rec_atoms = [], [], []
+            for lig_in, rec_in in chunk:
+                lig_res, lig_all = _side(lig_in)
+                rec_res, rec_all = _side(rec_in)
+                lig, rec, lig_ca, rec_ca = FZ.preprocess_unbound_bound(lig_res, rec_res, inference=True)
+                gl, gr = FZ.protein_to_graph_unbound_bound(lig, rec, lig_ca, rec_ca, cutoff=cutoff,
+                                                           max_neighbor=max_neighbor, device=dev)
+                pairs.append((dict(gl, new_x=gl['x']), gr))
+                lig_atoms.append(torch.from_numpy(np.ascontiguousarray(lig_all, dtype=np.float32)).to(dev))
+                rec_atoms.append(torch.from_numpy(np.ascontiguousarray(rec_all, dtype=np.float32)).to(dev))
+            batch = G.batch_pairs(pairs).to(dev)
+            _sync(dev)
+            t1 = time.perf_counter()
+            with torch.no_grad():
+                _, _, _, rots, trs = net(batch, epoch=0)
+            _sync(dev)
+            t2 = time.perf_counter()
+            docked = [INF.apply_rigid(rots[i], trs[i], lig_atoms[i]) for i in range(len(chunk))]
+            _sync(dev)
+            t3 = time.perf_counter()
+            if remove_clashes:
+                caps = max_it if np.ndim(max_it) == 0 else list(max_it)[b0:b0 + len(chunk)]
+                cl = remove_clashes_batch(docked, rec_atoms, sigma=sigma, surface_ct=surface_ct, loss_stop=loss_stop,
+                                          max_it=caps, check_every=check_every)
+            else:
+                cl = [None] * len(chunk)
+            _sync(dev)
+            t4 = time.perf_counter()
+            times = {'graphs': t1 - t0, 'model': t2 - t1, 'rigid': t3 - t2, 'clashes': t4 - t3, 'total': t4 - t0,
+                     'n_complexes': len(chunk)}
+            for i in range(len(chunk)):
+                results.append({'rotation': rots[i].detach().cpu().numpy(), 'translation': trs[i].detach().cpu().numpy().reshape(3),
+                                'ligand_atoms_docked': docked[i],
+                                'ligand_atoms': cl[i]['positions'] if cl[i] is not None else docked[i],
+                                'clash_iterations': cl[i]['iterations'] if cl[i] is not None else 0,
+                                'clash_loss': cl[i]['loss'] if cl[i] is not None else None,
+                                'n_ligand_atoms': int(lig_atoms[i].shape[0]), 'n_receptor_atoms': int(rec_atoms[i].shape[0]),
+                                'batch_seconds': times})
+    finally:
+        net.train(was_training)
+    return results
+
+
+# ---- command line -------------------------------------------------------------------------------------------------
+def _stats(v):
+    a = np.asarray(v, dtype=np.float64)
+    return float(np.median(a)), float(np.mean(a)), float(np.std(a))
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(prog='python -m equidock_public_amd.dock',
+                                description="EquiDock rigid docking of a directory of complexes (src/inference_rigid.py) "
+                                            "with batched graph -> model -> clash removal on the MI355X.")
+    p.add_argument('--checkpoint', required=True, help="reference checkpoint {'args', 'state_dict'} (*_model_best.pth)")
+    p.add_argument('--input-dir', required=True, help='ligands to dock: <name>_l_b.pdb')
+    p.add_argument('--gt-dir', required=True, help='<name>_r_b_COMPLEX.pdb (receptor) and, optionally, '
+                                                   '<name>_l_b_COMPLEX.pdb (ground-truth ligand for CRMSD / IRMSD)')
+    p.add_argument('--out-dir', required=True)
+    p.add_argument('--remove-clashes', action='store_true', help='run the clash-removal loop (src/inference_rigid.py:207-234)')
+    p.add_argument('--batch', type=int, default=0, help='complexes per batch (default: all)')
+    p.add_argument('--max-it', type=int, default=2000)
+    p.add_argument('--device', default='cuda:0')
+    a = p.parse_args(argv)
+    try:
+        names = sorted(os.path.basename(f)[:-len('_l_b.pdb')] for f in glob.glob(os.path.join(a.input_dir, '*_l_b.pdb')))
+        if not names:
+            raise FileNotFoundError(f"no *_l_b.pdb files in {a.input_dir}")
+        complexes = []
+        for nm in names:
+            rec = os.path.join(a.gt_dir, nm + '_r_b_COMPLEX.pdb')
+            if not os.path.isfile(rec):
+                raise FileNotFoundError(f"{rec} is missing (receptor of {nm})")
+            complexes.append((os.path.join(a.input_dir, nm + '_l_b.pdb'), rec))
+        os.makedirs(a.out_dir, exist_ok=True)
+        dev = torch.device(a.device)
+        net = load_checkpoint(a.checkpoint, dev)
+        ca = net.checkpoint_args
+        t0 = time.perf_counter()
+        res = dock_complexes(net, complexes, remove_clashes=a.remove_clashes, max_complexes_per_batch=a.batch or None,
+                             device=dev, cutoff=float(ca.get('graph_cutoff', 30.0)),
+                             max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it)
+        suffix = '_EQUIDOCK_NO_CLASHES.pdb' if a.remove_clashes else '_EQUIDOCK.pdb'
+        crmsd, irmsd = [], []
+        for nm, (lig_path, rec_path), r in zip(names, complexes, res):
+            out = os.path.join(a.out_dir, nm + '_l_b' + suffix)
+            INF.write_pdb_coordinates(lig_path, r['ligand_atoms'], out)
+            line = (f"{nm}: {r['n_ligand_atoms']} ligand atoms, {r['n_receptor_atoms']} receptor atoms -> {out}")
+            if a.remove_clashes:
+                line += f"  clash iterations {r['clash_iterations']}, loss {r['clash_loss']:.4f}"
+            gt = os.path.join(a.gt_dir, nm + '_l_b_COMPLEX.pdb')
+            if os.path.isfile(gt):
+                rec_ca = INF.read_pdb_atoms(rec_path, ca_only=True)
+                c, i = INF.complex_and_interface_rmsd(INF.read_pdb_atoms(out, ca_only=True), rec_ca,
+                                                      INF.read_pdb_atoms(gt, ca_only=True), rec_ca)
+                crmsd.append(c)
+                irmsd.append(i)
+                line += f"  CRMSD {c:.3f}  IRMSD {i:.3f}"
+            print(line, flush=True)
+        wall = time.perf_counter() - t0
+        print(f"Mean runtime: {wall / len(res):.4f} s per complex ({len(res)} complexes, {wall:.3f} s)")
+        if crmsd:
+            print("CRMSD median/mean/std: %.3f / %.3f / %.3f" % _stats(crmsd))
+            print("IRMSD median/mean/std: %.3f / %.3f / %.3f" % _stats(irmsd))
+    except Exception as e:          # noqa: BLE001 - a command-line tool: report and exit non-zero
+        print(f"error: {type(e).__name__}: {e}", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
