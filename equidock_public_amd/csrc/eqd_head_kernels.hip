@@ -825,8 +825,7 @@ __global__ __launch_bounds__(64) void k_kabsch_bwd(int B, int K, const float* __
                                                    const float* __restrict__ A_in, const float* __restrict__ T,
                                                    const float* __restrict__ dT, const float* __restrict__ db,
                                                    const float* __restrict__ dYl_ext,
-                                                   const float* __restrict__ dYr_ext, int use_ext,
-                                                   float* __restrict__ dY, const int32_t* __restrict__ seg_off,
+                                                   const float* __restrict__ dYr_ext, float* __restrict__ dY, const int32_t* __restrict__ seg_off,
                                                    const float* __restrict__ x0, const float* __restrict__ d_lig,
                                                    const double* __restrict__ usv) {
     const int p = blockIdx.x, t = threadIdx.x;
@@ -977,13 +976,9 @@ __global__ __launch_bounds__(64) void k_kabsch_bwd(int B, int K, const float* __
         for (int i = 0; i < 3; ++i) {
             const float vr = gr[kk][i] - gmr[i] + (float)(dbv[i] * (double)invK);
             const float vl = gl[kk][i] - gml[i] + (float)(dml[i] * (double)invK);
-            if (use_ext) {   // dY = external gradient (or 0) + Kabsch path; no pre-initialised buffer needed
-                dYr[k * 3 + i] = vr + (dYr_ext ? dYr_ext[(size_t)p * K * 3 + k * 3 + i] : 0.f);
-                dYl[k * 3 + i] = vl + (dYl_ext ? dYl_ext[(size_t)p * K * 3 + k * 3 + i] : 0.f);
-            } else {
-                dYr[k * 3 + i] += vr;
-                dYl[k * 3 + i] += vl;
-            }
+            // dY = external gradient (or 0) + Kabsch path; no pre-initialised buffer needed
+            dYr[k * 3 + i] = vr + (dYr_ext ? dYr_ext[(size_t)p * K * 3 + k * 3 + i] : 0.f);
+            dYl[k * 3 + i] = vl + (dYl_ext ? dYl_ext[(size_t)p * K * 3 + k * 3 + i] : 0.f);
         }
     }
 }
@@ -1000,7 +995,7 @@ extern "C" int eqd_kabsch_bwd(int n_pairs, int n_heads, const float* Y, const fl
         return EQD_ERR_UNSUPPORTED;
     }
     hipLaunchKernelGGL(k_kabsch_bwd, dim3(n_pairs), dim3(64), 0, (hipStream_t)stream, n_pairs, n_heads, Y,
-                       A, T, dT, db, (const float*)nullptr, (const float*)nullptr, 0, dY, (const int32_t*)nullptr,
+                       A, T, dT, db, (const float*)nullptr, (const float*)nullptr, dY, (const int32_t*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, (const double*)nullptr);
     return eqd_check_launch("k_kabsch_bwd");
 }
@@ -1018,7 +1013,7 @@ int eqd_kabsch_bwd_impl(int n_pairs, int n_heads, const float* Y, const float* A
         return EQD_ERR_UNSUPPORTED;
     }
     hipLaunchKernelGGL(k_kabsch_bwd, dim3(n_pairs), dim3(64), 0, (hipStream_t)stream, n_pairs, n_heads, Y,
-                       A, T, dT, db, dYl_ext, dYr_ext, 1, dY, g ? g->seg_off : (const int32_t*)nullptr,
+                       A, T, dT, db, dYl_ext, dYr_ext, dY, g ? g->seg_off : (const int32_t*)nullptr,
                        g ? g->x0 : (const float*)nullptr, g ? d_lig : (const float*)nullptr, usv);
     return eqd_check_launch("k_kabsch_bwd");
 }

@@ -75,9 +75,10 @@ BF16_OUT_TOL, BF16_GRAD_L2, BF16_GRAD_MX = 2e-2, 6e-2, 1.2e-1
 BF16_ROT_SCALE = 10.0
 
 
-def _oracle_run(sd, args, raw, faithful, loss_fn, mode, given=None, dtype=None):
+def _oracle_run(sd, args, raw, faithful, loss_fn, mode, given=None, dtype=None, rand_fn=None):
     """One oracle evaluation (outputs, parameter gradients of `loss_fn`) under a Kink mode.  dtype=torch.float64: the same
-    op sequence in double precision (parameters and inputs converted) - the yardstick for the fp32 noise floor of an input."""
+    op sequence in double precision (parameters and inputs converted) - the yardstick for the fp32 noise floor of an input.
+    rand_fn: the Kabsch guard's draws (port.kabsch)."""
     port.Kink.mode, port.Kink.near, port.Kink.given, port.Kink.flips = mode, 0, given, []
     try:
         uniq = {}       # shared layers: one leaf per distinct tensor, so that its gradient is the sum over the layers
@@ -85,7 +86,7 @@ def _oracle_run(sd, args, raw, faithful, loss_fn, mode, given=None, dtype=None):
         leaves = {k: uniq.setdefault(id(v), cv(v).requires_grad_(True)) for k, v in sd.items()}
         if dtype is not None:
             raw = {k: (v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in raw.items()}
-        outs = port.forward(leaves, args, raw, faithful=faithful)
+        outs = port.forward(leaves, args, raw, faithful=faithful, rand_fn=rand_fn)
         loss_fn(outs).backward()
         grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
         return outs, grads, port.Kink.near, port.Kink.flips
@@ -156,12 +157,13 @@ FLIP_RATE_MAX_BF16 = 1e-2        # at most 1 % of all decisions may differ in bf
 FLIP_BELOW_2M8_BF16 = 0.99       # ... and at least 99 % of those that do sit below 2^-8 of the tensor's largest pre-activation
 
 
-def oracle_given(net, g, sd, args, raw, faithful=True, loss_fn=None, flip_rel_max=FLIP_REL_MAX, dtype=None):
+def oracle_given(net, g, sd, args, raw, faithful=True, loss_fn=None, flip_rel_max=FLIP_REL_MAX, dtype=None, rand_fn=None):
     """Oracle outputs + gradients evaluated with the library's own LeakyReLU decisions (oracle.iegmn_port.Kink 'given'):
     ONE gradient, compared plainly.  Returns (outs, grads, flips) - flips = [(tag, count, largest |z| / max|z|)] where the
     library's decision differs from the oracle's own sign; asserted to be at rounding level."""
     given = library_signs(net, g)
-    outs, grads, _, flips = _oracle_run(sd, args, raw, faithful, loss_fn or port.scalar_loss, 'given', given, dtype=dtype)
+    outs, grads, _, flips = _oracle_run(sd, args, raw, faithful, loss_fn or port.scalar_loss, 'given', given, dtype=dtype,
+                                        rand_fn=rand_fn)
     for tag, n, rel in flips:
         assert rel <= flip_rel_max, f'LeakyReLU mask differs from the oracle at a pre-activation of relative size {rel:.2e}: {tag} ({n})'
     return outs, grads, flips
@@ -237,17 +239,21 @@ def hull_diagnostics(net, sd, args, raw, faithful):
 
 
 def check_model_vs_oracle(dev, sizes, layers=8, seed=3, pair_seed=33, faithful=True, what='', args_over=None,
-                          l2=GRAD_L2, mx=GRAD_MX, tol=1e-4, report=None, bf16=False, rot_scale=40.0):
+                          l2=GRAD_L2, mx=GRAD_MX, tol=1e-4, report=None, bf16=False, rot_scale=40.0, svd_draws=None,
+                          svd_status=None):
     """Whole model (outputs + every parameter gradient of the fixed scalar loss) on seeded synthetic pairs of the given
     sizes against the oracle on the host evaluated with the library's own LeakyReLU decisions (oracle_given).  bf16=True: the HIP path in its bf16
-    mode against the oracle with the same rounding points."""
+    mode against the oracle with the same rounding points.  svd_draws [B, 10, 3]: the Kabsch guard's draws for both, the
+    guard iterations per pair must then be svd_status (otherwise the guard must not fire)."""
     args = port.default_args(**dict(dict(iegmn_n_lays=layers, skip_weight_h=0.75), **(args_over or {})))
     sd = port.init_state_dict(args, seed=seed, rot_scale=rot_scale)
     net = build_model(dict(args, hip_storage_dtype='bf16') if bf16 else args, sd, dev)
+    if svd_draws is not None:
+        net.iegmn_original.svd_draws = svd_draws
     port.Bf16Mode.on = bool(bf16)
     try:
         return _check_model_vs_oracle(dev, net, args, sd, sizes, layers, pair_seed, faithful, what, l2, mx, tol, report,
-                                      FLIP_REL_MAX_BF16 if bf16 else FLIP_REL_MAX)
+                                      FLIP_REL_MAX_BF16 if bf16 else FLIP_REL_MAX, svd_draws, svd_status)
     finally:
         port.Bf16Mode.on = False
 
@@ -441,8 +447,10 @@ HEAD_L2, HEAD_MX = 3e-4, 1.5e-3
 HEAD_L2_BF16, HEAD_MX_BF16 = 4e-3, 1.5e-2      # d h_L / mlp_h_mean_ROT pass one bf16-input GEMM in bf16 mode (2^-9 per input)
 
 
-def check_head_backward(dev, sizes, layers=8, seed=3, pair_seed=34, bf16=False, what='', report=None, rot_scale=40.0):
-    args = port.default_args(iegmn_n_lays=layers, skip_weight_h=0.75)
+def check_head_backward(dev, sizes, layers=8, seed=3, pair_seed=34, bf16=False, what='', report=None, rot_scale=40.0,
+                        num_att_heads=None):
+    over = {} if num_att_heads is None else dict(num_att_heads=num_att_heads)
+    args = port.default_args(iegmn_n_lays=layers, skip_weight_h=0.75, **over)
     sd = port.init_state_dict(args, seed=seed, rot_scale=rot_scale)
     net = build_model(dict(args, hip_storage_dtype='bf16') if bf16 else args, sd, dev)
     g = G.batch_pairs(synthetic.make_pairs(list(sizes), pair_seed)).to(dev)
@@ -504,17 +512,32 @@ def check_head_backward(dev, sizes, layers=8, seed=3, pair_seed=34, bf16=False, 
         report.append(line)
 
 
+def _guard_rand_fn(draws, status):
+    """port.kabsch's rand_fn replaying the library's draws [B, 10, 3]: the pairs on which the guard fires call it in
+    batch order, each from num_it = 0."""
+    fired = iter([p for p, n in enumerate(status) if n > 0])
+    cur = [None]
+
+    def rand_fn(num_it):
+        if num_it == 0:
+            cur[0] = next(fired)
+        return torch.diag(draws[cur[0], num_it].detach().cpu().float())
+    return rand_fn
+
+
 def _check_model_vs_oracle(dev, net, args, sd, sizes, layers, pair_seed, faithful, what, l2, mx, tol, report,
-                           flip_rel_max=FLIP_REL_MAX):
+                           flip_rel_max=FLIP_REL_MAX, svd_draws=None, svd_status=None):
     pairs = synthetic.make_pairs(list(sizes), pair_seed)
     g = G.batch_pairs(pairs).to(dev)
     outs = net(g, epoch=0)
     port.scalar_loss(outs).backward()
     sync(dev)
-    assert net.iegmn_original.last_svd_status.cpu().tolist() == [0] * len(sizes), 'SVD guard fired'
+    status = list(svd_status) if svd_draws is not None else [0] * len(sizes)
+    assert net.iegmn_original.last_svd_status.cpu().tolist() == status, 'SVD guard iterations'
     raw = port.raw_from_graph(g)
     # the oracle with the library's own LeakyReLU decisions: one gradient, compared plainly
-    ref, grads, flips = oracle_given(net, g, sd, args, raw, faithful=faithful, flip_rel_max=flip_rel_max)
+    rand_fn = None if svd_draws is None else _guard_rand_fn(svd_draws, status)
+    ref, grads, flips = oracle_given(net, g, sd, args, raw, faithful=faithful, flip_rel_max=flip_rel_max, rand_fn=rand_fn)
     worst = 0.0
     for nm, a, b in zip(('lig', 'Yl', 'Yr', 'T', 'b'), outs, ref):
         got, exp = cat_out(a), cat_out(b)
