@@ -120,6 +120,51 @@ __device__ __forceinline__ void kernarg_to_lds(T& dst, const void* kernarg, int 
     for (int i = threadIdx.x; i < (int)(sizeof(T) / 4); i += blockDim.x) ((int*)&dst)[i] = src[i];
 }
 
+// ---- LDS-DMA (gfx950 global_load_lds_dwordx4): global memory -> LDS with no register in between -------------------
+// glds16: every lane names its own 16-byte source; the 64 pieces land at lds_base + 16 * lane (lds_base wave-uniform), so
+// one instruction fills 1 KiB of LDS linearly - an image that wants a bank swizzle permutes the SOURCE addresses and
+// applies the same permutation when it reads.  The copy is asynchronous: it counts on the wave's vmcnt like a load.  Its
+// bytes may be read by the issuing wave after vm_wait<N>() has retired it (N = vector-memory operations issued AFTER it
+// that may stay in flight), by other waves after a barrier behind that wait.  lds_barrier() is the barrier that leaves
+// later copies in flight: __syncthreads() waits vmcnt(0) while one is pending.  keep_after_wait(v) pins a value that an
+// ORDINARY load requested before the copies: its first use (and the compiler's own full wait for it) stays behind the
+// vm_wait it is placed after.  On the host simulator the copy happens at issue time and the waits are no-ops.
+#ifdef EQD_HOSTSIM
+__device__ __forceinline__ void glds16(const float* gsrc, float* lds_base) {
+    __builtin_memcpy(lds_base + 4 * (threadIdx.x & 63), gsrc, 16);
+}
+template <int N>
+__device__ __forceinline__ void vm_wait() { static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit count"); }
+__device__ __forceinline__ void lds_barrier() { __syncthreads(); }
+template <class T>
+__device__ __forceinline__ void keep_after_wait(T&) {}
+#else
+// (inline assembly, not __builtin_amdgcn_global_load_lds: the compiler tracks the builtin's LDS write and puts a full
+//  s_waitcnt vmcnt(0) in front of the first LDS read that may alias it - with two dozen copies in flight that is the wait
+//  for ALL of them where a counted one was meant.  M0 carries the LDS destination; it is the compiler's register, so it is
+//  saved and restored inside the statement.  The compiler does not count these copies: every wait for them is a vm_wait.)
+__device__ __forceinline__ void glds16(const float* gsrc, float* lds_base) {
+    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds_base);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(dst)
+                 : "memory");
+}
+template <int N>
+__device__ __forceinline__ void vm_wait() {
+    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit count");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+template <class T>
+__device__ __forceinline__ void keep_after_wait(T& v) { asm volatile("" : "+v"(v)); }
+#endif
+
 // ---- bf16 MFMA path (edge-message kernels, storage_bf16 mode) ---------------------------------------------------
 // v_mfma_f32_16x16x16_bf16: lane (i = lane & 15, g = lane >> 4) supplies A[i][4g..4g+3] and B[4g..4g+3][i] as 4 bf16
 // and receives D[4g + r][i] - the same D layout as the fp32 instruction, so with features on the M axis an output

@@ -8,8 +8,10 @@
 #include "eqd_rowwave_inl.h"
 #include "eqd_rowres_inl.h"
 #include "eqd_rowres80_inl.h"
+#include "eqd_chainres_inl.h"
 #include "eqd_gather_inl.h"
 
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -976,6 +978,33 @@ static int launch_rowwave(const EqdChainArg& arg, int rows, bool bf, hipStream_t
     return eqd_check_launch("k_rowwave");
 }
 
+// k_rowchain_res_fwd (eqd_chainres_inl.h): the forward node chain of a 64-wide layer, weights and rows resident in LDS, where
+// k_rowchain<1, false, 1> runs otherwise (one tile per workgroup, no more tiles than CUs, fp32).  EQD_CHAIN_RESIDENT=0
+// keeps k_rowchain (A/B runs, the bit comparisons of tests/test_chain_resident_*.py).  The copies move 16 bytes per lane
+// from the addresses the register loads of k_rowchain use - 4-byte aligned where a row is 261 or 69 floats long.
+static int chain_resident_on() {
+    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT");
+    return !(f && f[0] == '0' && f[1] == 0);
+}
+static bool cr_fwd_eligible(const EqdChainJob* jobs, int njobs, int rows) {
+    if (!chain_resident_on() || njobs != 2 || rows <= 0 || eqd_row_tiles(rows) != 1 || eqd_rowchain_blocks(rows) > eqd_num_cus()) return false;
+    const EqdChainJob &C0 = jobs[0], &C1 = jobs[1];
+    const EqdLinJob &J0 = C0.lin, &J1 = C1.lin;
+    if (C0.type != 0 || C1.type != 0 || J0.bf16 || J1.bf16 || J0.rows != rows || J1.rows != rows) return false;
+    if (J0.M != 64 || J0.nsrc != 4 || C0.out_local != 0 || !J0.ln_g || !J0.ln_b || J0.R) return false;
+    for (int s = 0; s < 4; ++s) {
+        const EqdLinSrc& S = J0.s[s];
+        if (!S.X || !S.W || S.mask || S.w_cs != 1 || C0.src_local[s] >= 0) return false;
+        if (s < 3 ? S.K != 64 : (S.K <= 64 || S.K > 80)) return false;
+    }
+    if (J1.M != 64 || J1.nsrc != 1 || C1.src_local[0] != 0 || C1.out_local >= 0 || J1.ln_g || J1.mul || J1.pre_ln) return false;
+    if (J1.s[0].K != 64 || !J1.s[0].W || J1.s[0].mask || J1.s[0].w_cs != 1) return false;
+    return true;
+}
+static std::atomic<long long> g_chain_resident_launches{0};
+// how many row chains this process has launched on the resident-weights body (tests: which body ran)
+extern "C" long long eqd_chain_resident_launches(void) { return g_chain_resident_launches.load(); }
+
 int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_t st, int* partial_rows) {
     if (njobs <= 0 || njobs > EQD_CHAIN_MAXJOBS) {
         eqd_set_error("eqd_launch_rowchain: %d jobs (1..%d)", njobs, EQD_CHAIN_MAXJOBS);
@@ -1018,6 +1047,14 @@ int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_
         return launch_rowwave(arg, rows, bf, st);
     }
     if (partial_rows) *partial_rows = eqd_rowchain_blocks(rows);
+    {
+        const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");      // (a forced register budget means: this experiment wants k_rowchain)
+        if (!(oc && oc[0]) && cr_fwd_eligible(jobs, njobs, rows)) {
+            hipLaunchKernelGGL(k_rowchain_res_fwd, dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
+            g_chain_resident_launches.fetch_add(1);
+            return eqd_check_launch("k_rowchain");
+        }
+    }
     if (eqd_row_tiles(rows) == 2) {
         // (the two-tile forms need more than 256 registers: one workgroup per CU at every size)
         if (bf) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain<2, true, 1>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);

@@ -57,10 +57,14 @@ int eqd_tile_edges(void);
 int eqd_is_simulator(void);
 /* The EQD_* environment switches that select kernel forms for tests and A/B measurements (EQD_FUSE_FWD, EQD_FUSE_GATHER,
  * EQD_ATT_SPLIT, EQD_ATT_BWD_SPLIT, EQD_ATT_LB, EQD_ATT_LB_NB, EQD_ATT_DS, EQD_ATT_QDS_NB, EQD_ROWWAVE, EQD_ROW_TILES,
- * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
+ * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
  * agree on the forms they run.  A caller that changes one of them afterwards calls this to make the library forget its
  * snapshot (nothing in the reference corresponds to it). */
 void eqd_tunables_reload(void);
+/* Test aid: how many row chains this process has launched on the resident-weights body (k_rowchain_res_fwd: the forward node
+ * chain of a 64-wide layer with all weights in LDS, taken where k_rowchain<1, false, 1> runs otherwise; EQD_CHAIN_RESIDENT=0
+ * keeps k_rowchain).  Counts launches, also those recorded into a captured graph, not replays. */
+long long eqd_chain_resident_launches(void);
 /* Test aid: one 256-thread workgroup runs the library's cross-lane helpers (DPP moves, v_permlane{16,32}_swap) on in256
  * [256] beside the plain ds_bpermute forms, and the guard-free exponentials of the softmax kernels beside expf / exp2f;
  * mismatch [4] (device ints, zeroed by the caller) receives the number of differing (lane, check) pairs of the exchanges [0],
