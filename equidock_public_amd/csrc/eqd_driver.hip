@@ -220,9 +220,12 @@ int node_atb_jobs(const Dims& D, int l, const EqdModelDesc* m, const Saved* S, c
     auto ybf = [&](EqdAtbJob& J, const uint16_t* Yb, int ldy) {
         J.Y = (const float*)Yb; J.ldy = ldy; J.y_bf16 = 1;
     };
-    jobs[n++] = atb_job(dHout, D.dh, D.dh, Ls ? Ls->a1n : nullptr, d, d, N, G(P_WN2), d, G(P_BN2), m->lrelu_slope,
-                        nullptr, alpha);
-    if (bfs) ybf(jobs[n - 1], Ls->a1n_b, Ls->ld_a1n);
+    // (skip_weight_h == 0: node_mlp.4 receives no gradient, and EqdAtbJob.scale cannot say so - 0 means 1 there)
+    if (alpha != 0.f) {
+        jobs[n++] = atb_job(dHout, D.dh, D.dh, Ls ? Ls->a1n : nullptr, d, d, N, G(P_WN2), d, G(P_BN2), m->lrelu_slope,
+                            nullptr, alpha);
+        if (bfs) ybf(jobs[n - 1], Ls->a1n_b, Ls->ld_a1n);
+    }
     // (order: the jobs that share dz back to back, then the six that share h - eqd_atb runs units that are neighbours in
     // the list on the same XCD at about the same time, so a shared operand's rows are fetched into that L2 once)
     // node_mlp.0: four column segments [h | aggr_msg | aggr_cross | h0]
@@ -1143,8 +1146,10 @@ void node_update_atb_jobs(int rows, const EqdNodeUpdateParams* p, const float* h
     const int d = p->d_in, ldn = p->d0 + 2 * d + 64;
     const float alpha = d == p->d_out ? p->skip_weight_h : 1.f;
     int n = 0;
-    jobs[n++] = atb_job(d_h_out, p->d_out, p->d_out, a1n, d, d, rows, gr ? gr->dWn2 : nullptr, d, gr ? gr->dbn2 : nullptr,
-                        p->slope, nullptr, alpha);
+    // (skip_weight_h == 0: dWn2 and dbn2 receive nothing, and EqdAtbJob.scale cannot say so - 0 means 1 there)
+    if (alpha != 0.f)
+        jobs[n++] = atb_job(d_h_out, p->d_out, p->d_out, a1n, d, d, rows, gr ? gr->dWn2 : nullptr, d, gr ? gr->dbn2 : nullptr,
+                            p->slope, nullptr, alpha);
     jobs[n++] = atb_job(dz, d, d, aggr_msg, 64, 64, rows, gr ? gr->dWn1 + d : nullptr, ldn, nullptr, p->slope);
     if (aggr_cross || !gr)
         jobs[n++] = atb_job(dz, d, d, aggr_cross, p->ld_cross, d, rows, gr ? gr->dWn1 + d + 64 : nullptr, ldn, nullptr, p->slope);

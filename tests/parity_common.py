@@ -1973,7 +1973,8 @@ def check_node_update(dev, rows=301):
         lv = [t.clone().requires_grad_(True) for t in host]
         h_, am_, ac_, h0_, W1_, b1_, lg_, lb_, W2_, b2_ = lv
         z = F.leaky_relu(F.linear(torch.cat([h_, am_, ac_[:, :d], h0_], 1), W1_, b1_), 0.01)
-        u = F.linear(F.layer_norm(z, (d,), lg_, lb_, 1e-5), W2_, b2_)
+        a1 = F.layer_norm(z, (d,), lg_, lb_, 1e-5)
+        u = F.linear(a1, W2_, b2_)
         ref = s * u + (1 - s) * h_ if d == dout else u
         w = torch.randn(rows, dout)
         (ref * w).sum().backward()
@@ -1990,6 +1991,7 @@ def check_node_update(dev, rows=301):
         sync(dev)
         close(h_out, ref, what=f'node_update d={d} cross={cross} h_out')
         close(y_act, z, what=f'node_update d={d} y_act')
+        close(a1n, a1, what=f'node_update d={d} a1n')      # an output of the ABI, and state of the backward
         wsb = lib().eqd_node_update_bwd_workspace_bytes(rows, C.byref(prm))
         assert wsb > 0
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
