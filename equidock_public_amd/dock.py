@@ -1,6 +1,7 @@
 """Batched docking inference: src/inference_rigid.py's loop over a directory of complexes (:85-245) for N complexes at once.
 
-    graphs (per complex, device)  ->  one batched eval forward per chunk  ->  apply_rigid to each ligand's atoms
+    graphs of all complexes in one device pass (protein_graphs_batch)  ->  one batched eval forward per chunk
+    ->  apply_rigid to each ligand's atoms
     ->  remove_clashes_batch: clash removal of ALL complexes in one device loop (libequidock_dock.so), each stopping on
         its own  ->  PDB files and, with ground truth, the CRMSD / IRMSD summary
 
@@ -23,6 +24,7 @@ from . import _lib, config, featurize as FZ, graph as G, inference as INF
 HERE = os.path.dirname(os.path.abspath(__file__))
 DOCK_LIB_PATH = os.path.join(HERE, 'libequidock_dock.so')
 DOCK_ABI_VERSION = 1
+DOCK_GRAPH_ABI = 1
 
 _dock = None
 _dock_is_sim = False
@@ -41,6 +43,18 @@ def _declare(lib):
     lib.eqd_dock_clash_iterations.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                               C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                               C.c_void_p]
+    lib.eqd_dock_graph_abi.restype = C.c_int
+    lib.eqd_dock_graph_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_graph_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.eqd_dock_graph_init.restype = C.c_int
+    lib.eqd_dock_graph_init.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_graph_select.restype = C.c_int
+    lib.eqd_dock_graph_select.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_graph_edges.restype = C.c_int
+    lib.eqd_dock_graph_edges.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 
 
 def _bind(path):
@@ -49,6 +63,8 @@ def _bind(path):
     _declare(lib)
     if lib.eqd_dock_abi_version() != DOCK_ABI_VERSION:
         raise _lib.EquidockHipError(f"{path}: dock ABI version {lib.eqd_dock_abi_version()} != {DOCK_ABI_VERSION}")
+    if lib.eqd_dock_graph_abi() != DOCK_GRAPH_ABI:
+        raise _lib.EquidockHipError(f"{path}: dock graph ABI {lib.eqd_dock_graph_abi()} != {DOCK_GRAPH_ABI}")
     _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
     return lib
 
@@ -83,7 +99,7 @@ def _require_device(t, what):
         if t.is_cuda:
             raise _lib.EquidockHipError(f"{what}: the host simulator only takes CPU tensors")
     elif not t.is_cuda:
-        raise _lib.EquidockHipError(f"{what} is on {t.device}: batched clash removal runs only on an MI355X through "
+        raise _lib.EquidockHipError(f"{what} is on {t.device}: batched docking inference runs only on an MI355X through "
                                     "libequidock_dock.so (no CPU fallback)")
     return t
 
@@ -158,6 +174,127 @@ def remove_clashes_batch(ligand_atoms_list, receptor_atoms_list, sigma=8.0, surf
     return out
 
 
+# ---- batched graph construction -------------------------------------------------------------------------------------
+GRAPH_KEYS = ('x', 'res_feat', 'mu_r_norm', 'src', 'dst', 'he')
+last_graph_stats = {}      # of the latest protein_graphs_batch call: proteins, residues, edges, pairs, pruned_pairs, pruning
+
+
+def graph_pruning_enabled():
+    """EQD_DOCK_GRAPH_PRUNE=0 turns the centroid-distance pruning of the distance phase off (same results either way)."""
+    return os.environ.get('EQD_DOCK_GRAPH_PRUNE', '1') != '0'
+
+
+def _int32_offsets(sizes, what):
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(sizes)
+    if off[-1] > np.iinfo(np.int32).max:
+        raise _lib.EquidockHipError(f"{int(off[-1])} {what} do not fit int32 offsets: split the batch")
+    return np.ascontiguousarray(off.astype(np.int32))
+
+
+def _staging(n, dtype, dev):
+    """Host buffer of one upload or download: pinned when the device is a GPU (torch caches pinned blocks)."""
+    return torch.empty(n, dtype=dtype, pin_memory=dev.type == 'cuda')
+
+
+def protein_graphs_batch(proteins, cutoff, max_neighbor, device, residue_loc_is_alphaC=True):
+    """featurize.protein_graph for a list of (residues, bound_ca) proteins in one device pass (eqd_dock_graph_*): host
+    preparation per protein as there (local frames, alignment onto the bound C-alpha array, ragged atoms, residue ids),
+    then one upload per dtype, one launch per phase for ALL proteins, one read of the counts and one download per dtype.
+    Returns one dict per protein with the keys and dtypes of protein_graph (device tensors, bit-identical to it) plus
+    'host': the same six arrays as numpy views of the downloaded buffers, which graph.batch_pairs takes as they are.
+    A residue without a neighbour under the cutoff raises ValueError naming the protein's index in the batch."""
+    global last_graph_stats
+    lib = load_dock_library()
+    proteins = list(proteins)
+    K = int(max_neighbor)
+    if K < 1 or K > 64:
+        raise ValueError("max_neighbor must be in 1..64")
+    if not proteins:
+        return []
+    dev = torch.device(device)
+    _require_device(torch.empty(0, device=dev), 'protein graph inputs')
+    P = len(proteins)
+    prep = []
+    for residues, bound_ca in proteins:
+        loc, n_i, u_i, v_i = FZ.local_frames(residues, residue_loc_is_alphaC)
+        R, t = FZ.rigid_transform_kabsch_3d(loc.T, np.asarray(bound_ca).T)
+        x = ((R @ loc.T) + t).T                     # float64 from here on, as in the reference
+        n_i, u_i, v_i = (R @ n_i.T).T, (R @ u_i.T).T, (R @ v_i.T).T
+        atoms, off = FZ.atoms_ragged(residues)
+        res = np.asarray([FZ.residue_type_id(r.resname) for r in residues], dtype=np.float32)
+        prep.append((atoms, off, x, n_i, u_i, v_i, res))
+    res_off = _int32_offsets([len(q[6]) for q in prep], 'residues')
+    patom_off = _int32_offsets([q[0].shape[0] for q in prep], 'atoms')
+    if 3 * int(patom_off[-1]) > np.iinfo(np.int32).max:
+        raise _lib.EquidockHipError(f"{int(patom_off[-1])} atoms do not fit int32 offsets: split the batch")
+    Rn, A = int(res_off[-1]), int(patom_off[-1])
+    ro, po = res_off.ctypes.data_as(C.c_void_p), patom_off.ctypes.data_as(C.c_void_p)
+    wsb = lib.eqd_dock_graph_workspace_bytes(P, ro, po, K)
+    if wsb == 0:
+        check(2)
+    # one staging buffer and one upload per dtype: fp32 = atoms | x | residue ids, fp64 = x | n | u | v, int32 = atom offsets
+    h32, h64, hi = _staging(3 * A + 4 * Rn, torch.float32, dev), _staging(12 * Rn, torch.float64, dev), _staging(Rn + 1, torch.int32, dev)
+    a32, a64, ai = h32.numpy(), h64.numpy().reshape(4, Rn, 3), hi.numpy()
+    ai[0] = 0
+    for p, (atoms, off, x, n_i, u_i, v_i, res) in enumerate(prep):
+        r0, r1, a0, a1 = int(res_off[p]), int(res_off[p + 1]), int(patom_off[p]), int(patom_off[p + 1])
+        a32[3 * a0:3 * a1] = atoms.reshape(-1)
+        a32[3 * A + 3 * r0:3 * A + 3 * r1] = x.astype(np.float32).reshape(-1)
+        a32[3 * A + 3 * Rn + r0:3 * A + 3 * Rn + r1] = res
+        for q, v in enumerate((x, n_i, u_i, v_i)):
+            a64[q, r0:r1] = v
+        ai[r0 + 1:r1 + 1] = off[1:] + a0
+    d32, d64, di = (h.to(dev, non_blocking=True) for h in (h32, h64, hi))
+    xs = d64.view(4, Rn, 3)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    deg = torch.empty(Rn, dtype=torch.int32, device=dev)
+    mu = torch.empty(Rn, 5, dtype=torch.float32, device=dev)
+    counts = torch.empty(2 * P + 2, dtype=torch.int32, device=dev)      # pruned pairs | edge offsets [P + 1] | no-neighbour [P]
+    prune = graph_pruning_enabled()
+    st = _stream(dev)
+    with _lib.device_guard(dev):
+        check(lib.eqd_dock_graph_init(P, ro, po, K, _lib.ptr(ws), C.c_size_t(wsb), st))
+        check(lib.eqd_dock_graph_select(P, ro, po, _lib.ptr(d32), _lib.ptr(di), _lib.ptr(xs[0]), C.c_double(float(cutoff)), K,
+                                        int(prune), _lib.ptr(deg), _lib.ptr(counts[1:]), _lib.ptr(mu), _lib.ptr(counts[P + 2:]),
+                                        _lib.ptr(counts), _lib.ptr(ws), C.c_size_t(wsb), st))
+    cnt = counts.cpu().numpy()                                          # device-to-host synchronisation 1 of 2
+    eoff, lonely = cnt[1:P + 2], cnt[P + 2:]
+    if (lonely >= 0).any():
+        # the reference asserts here (protein_utils.py:354, `assert len(valid_src) > 0`), and mu_r_norm would be 0 / 0
+        p = int(np.nonzero(lonely >= 0)[0][0])
+        raise ValueError(f"protein {p} of the batch: residue {int(lonely[p])} has no neighbour closer than cutoff={cutoff}: "
+                         "the reference asserts on such graphs (src/utils/protein_utils.py:354)")
+    E = int(eoff[P])
+    sd = torch.empty(2, E, dtype=torch.int32, device=dev)
+    he = torch.empty(E, 27, dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        check(lib.eqd_dock_graph_edges(P, ro, po, K, _lib.ptr(xs[0]), _lib.ptr(xs[1]), _lib.ptr(xs[2]), _lib.ptr(xs[3]),
+                                       _lib.ptr(sd[0]), _lib.ptr(sd[1]), _lib.ptr(he), _lib.ptr(ws), C.c_size_t(wsb), st))
+    if dev.type == 'cuda':
+        of, oi = _staging(27 * E + 5 * Rn, torch.float32, dev), _staging(2 * E, torch.int32, dev)
+        of[:27 * E].copy_(he.view(-1), non_blocking=True)
+        of[27 * E:].copy_(mu.view(-1), non_blocking=True)
+        oi.copy_(sd.view(-1), non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()                    # device-to-host synchronisation 2 of 2
+        he_h, mu_h, sd_h = of[:27 * E].numpy().reshape(E, 27), of[27 * E:].numpy().reshape(Rn, 5), oi.numpy().reshape(2, E)
+    else:
+        he_h, mu_h, sd_h = he.numpy(), mu.numpy(), sd.numpy()
+    x_d, res_d = d32[3 * A:3 * A + 3 * Rn].view(Rn, 3), d32[3 * A + 3 * Rn:].view(Rn, 1)
+    x_h, res_h = a32[3 * A:3 * A + 3 * Rn].reshape(Rn, 3), a32[3 * A + 3 * Rn:].reshape(Rn, 1)
+    out = []
+    for p in range(P):
+        r0, r1, e0, e1 = int(res_off[p]), int(res_off[p + 1]), int(eoff[p]), int(eoff[p + 1])
+        out.append({'x': x_d[r0:r1], 'res_feat': res_d[r0:r1], 'mu_r_norm': mu[r0:r1], 'src': sd[0, e0:e1],
+                    'dst': sd[1, e0:e1], 'he': he[e0:e1],
+                    'host': {'x': x_h[r0:r1], 'res_feat': res_h[r0:r1], 'mu_r_norm': mu_h[r0:r1], 'src': sd_h[0, e0:e1],
+                             'dst': sd_h[1, e0:e1], 'he': he_h[e0:e1]}})
+    n = np.diff(res_off).astype(np.int64)
+    last_graph_stats = {'proteins': P, 'residues': Rn, 'edges': E, 'pairs': int((n * (n - 1) // 2).sum()),
+                        'pruned_pairs': int(cnt[0]), 'pruning': prune}
+    return out
+
+
 # ---- model + files ------------------------------------------------------------------------------------------------
 def load_checkpoint(path, device):
     """Rigid_Body_Docking_Net from a reference checkpoint {'args', 'state_dict'} (src/inference_rigid.py:97-112): the
@@ -190,12 +327,36 @@ def _sync(dev):
         torch.cuda.synchronize(dev)
 
 
+def _chunk_graphs(chunk, cutoff, max_neighbor, dev):
+    """The graphs stage of dock_complexes for one chunk in one device pass: (pairs for graph.batch_pairs - host views, no
+    further download -, ligand atoms, receptor atoms); the atoms of all complexes go up in one copy."""
+    prots, sides = [], []
+    for lig_in, rec_in in chunk:
+        lig_res, lig_all = _side(lig_in)
+        rec_res, rec_all = _side(rec_in)
+        lig, rec, lig_ca, rec_ca = FZ.preprocess_unbound_bound(lig_res, rec_res, inference=True)
+        prots += [(lig, lig_ca), (rec, rec_ca)]
+        sides += [lig_all, rec_all]
+    gs = [g['host'] for g in protein_graphs_batch(prots, cutoff, max_neighbor, dev)]
+    pairs = [(dict(gs[2 * i], new_x=gs[2 * i]['x']), gs[2 * i + 1]) for i in range(len(chunk))]
+    aoff = _int32_offsets([len(a) for a in sides], 'atoms')
+    hall = _staging(3 * int(aoff[-1]), torch.float32, dev)
+    for i, a in enumerate(sides):
+        hall.numpy()[3 * aoff[i]:3 * aoff[i + 1]] = np.asarray(a, dtype=np.float32).reshape(-1)
+    dall = hall.to(dev, non_blocking=True).view(-1, 3)
+    return (pairs, [dall[aoff[2 * i]:aoff[2 * i + 1]] for i in range(len(chunk))],
+            [dall[aoff[2 * i + 1]:aoff[2 * i + 2]] for i in range(len(chunk))])
+
+
 def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=None, device=None, cutoff=30.0,
-                   max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50):
+                   max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50,
+                   batched_graphs=True):
     """Dock a list of (ligand, receptor) complexes, each side a PDB path or a list of featurize.Residue (the ligand's
     file / residues in their input pose, the receptor's in the bound pose - the reference's `*_l_b.pdb` and
     `*_r_b_COMPLEX.pdb`).  Per chunk of `max_complexes_per_batch` complexes (all at once by default): graphs on the
-    device, one batched eval forward, apply_rigid to every ligand atom, then remove_clashes_batch.
+    device, one batched eval forward, apply_rigid to every ligand atom, then remove_clashes_batch.  `batched_graphs`: all
+    graphs of a chunk from one protein_graphs_batch call (and the chunk's atoms in one upload) instead of a loop over
+    the complexes; the results are bit-identical either way.
 
     Returns one dict per complex: rotation [3, 3], translation [3] (numpy), ligand_atoms_docked (apply_rigid of all ligand
     atoms, before clash removal) and ligand_atoms (after it; the same tensor without clash removal), clash_iterations,
@@ -212,16 +373,19 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
             chunk = complexes[b0:b0 + step]
             _sync(dev)
             t0 = time.perf_counter()
-            pairs, lig_atoms, rec_atoms = [], [], []
-            for lig_in, rec_in in chunk:
-                lig_res, lig_all = _side(lig_in)
-                rec_res, rec_all = _side(rec_in)
-                lig, rec, lig_ca, rec_ca = FZ.preprocess_unbound_bound(lig_res, rec_res, inference=True)
-                gl, gr = FZ.protein_to_graph_unbound_bound(lig, rec, lig_ca, rec_ca, cutoff=cutoff,
-                                                           max_neighbor=max_neighbor, device=dev)
-                pairs.append((dict(gl, new_x=gl['x']), gr))
-                lig_atoms.append(torch.from_numpy(np.ascontiguousarray(lig_all, dtype=np.float32)).to(dev))
-                rec_atoms.append(torch.from_numpy(np.ascontiguousarray(rec_all, dtype=np.float32)).to(dev))
+            if batched_graphs:
+                pairs, lig_atoms, rec_atoms = _chunk_graphs(chunk, cutoff, max_neighbor, dev)
+            else:
+                pairs, lig_atoms, rec_atoms = [], [], []
+                for lig_in, rec_in in chunk:
+                    lig_res, lig_all = _side(lig_in)
+                    rec_res, rec_all = _side(rec_in)
+                    lig, rec, lig_ca, rec_ca = FZ.preprocess_unbound_bound(lig_res, rec_res, inference=True)
+                    gl, gr = FZ.protein_to_graph_unbound_bound(lig, rec, lig_ca, rec_ca, cutoff=cutoff,
+                                                               max_neighbor=max_neighbor, device=dev)
+                    pairs.append((dict(gl, new_x=gl['x']), gr))
+                    lig_atoms.append(torch.from_numpy(np.ascontiguousarray(lig_all, dtype=np.float32)).to(dev))
+                    rec_atoms.append(torch.from_numpy(np.ascontiguousarray(rec_all, dtype=np.float32)).to(dev))
             batch = G.batch_pairs(pairs).to(dev)
             _sync(dev)
             t1 = time.perf_counter()
@@ -274,6 +438,8 @@ def main(argv=None):
     p.add_argument('--batch', type=int, default=0, help='complexes per batch (default: all)')
     p.add_argument('--max-it', type=int, default=2000)
     p.add_argument('--device', default='cuda:0')
+    p.add_argument('--no-batched-graphs', action='store_true',
+                   help='build the graphs in a loop over the complexes instead of one device pass per batch (same results)')
     a = p.parse_args(argv)
     try:
         names = sorted(os.path.basename(f)[:-len('_l_b.pdb')] for f in glob.glob(os.path.join(a.input_dir, '*_l_b.pdb')))
@@ -292,7 +458,8 @@ def main(argv=None):
         t0 = time.perf_counter()
         res = dock_complexes(net, complexes, remove_clashes=a.remove_clashes, max_complexes_per_batch=a.batch or None,
                              device=dev, cutoff=float(ca.get('graph_cutoff', 30.0)),
-                             max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it)
+                             max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it,
+                             batched_graphs=not a.no_batched_graphs)
         suffix = '_EQUIDOCK_NO_CLASHES.pdb' if a.remove_clashes else '_EQUIDOCK.pdb'
         crmsd, irmsd = [], []
         for nm, (lig_path, rec_path), r in zip(names, complexes, res):

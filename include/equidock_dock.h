@@ -59,6 +59,53 @@ EQD_DOCK_API int eqd_dock_clash_iterations(int n_iter, int n_complex, const int3
                                            float loss_stop, EqdClashState* states, int32_t* n_done, void* workspace,
                                            size_t ws_bytes, void* stream);
 
+/*
+ * Batched graph construction: compute_dig_kNN_graph (src/utils/protein_utils.py:311-397; the arithmetic of
+ * eqd_protein_graph_distances / _select / _edges, include/equidock_hip.h) for P proteins in one device pass.  A
+ * protein's outputs are bit-identical to the single-protein entry points, alone, in any batch, at any position and
+ * from run to run.
+ *
+ * Layout: the proteins are stored one after another, R = res_off[P] residues and A atoms in all.
+ *   res_off [P + 1]        HOST int32, res_off[0] = 0: protein p = residues res_off[p] .. res_off[p + 1] - 1 (>= 1)
+ *   prot_atom_off [P + 1]  HOST int32, prot_atom_off[0] = 0: protein p's atoms (= atom_off at its first residue)
+ *   atoms [A][3] fp32, atom_off [R + 1] int32 (global atom rows of every residue)
+ *   x, n_i, u_i, v_i [R][3] fp64: aligned locations and frame vectors
+ * The three size arguments (P, the two host offset arrays, max_neighbor in 1..64) must be the same in every call on a
+ * workspace.  Sequence: workspace_bytes -> init (once) -> select -> the host reads edge_off[P] and no_neighbor ->
+ * edges with src / dst / he of edge_off[P] rows.
+ */
+#define EQD_DOCK_GRAPH_ABI 1
+EQD_DOCK_API int eqd_dock_graph_abi(void);
+
+/* Workspace of a batch with these host offsets; 0 when they are invalid or a size does not fit 32-bit offsets
+ * (eqd_dock_last_error says why). */
+EQD_DOCK_API size_t eqd_dock_graph_workspace_bytes(int n_protein, const int32_t* res_off, const int32_t* prot_atom_off,
+                                                   int max_neighbor);
+
+/* Validates the offsets and writes the batch's work-item table into the workspace (a host-to-device copy; this call
+ * waits for that copy). */
+EQD_DOCK_API int eqd_dock_graph_init(int n_protein, const int32_t* res_off, const int32_t* prot_atom_off,
+                                     int max_neighbor, void* workspace, size_t ws_bytes, void* stream);
+
+/* Enqueues centroids, distances, neighbour selection + mu_r_norm and the degree scan (one launch each, whatever P is; no
+ * host synchronisation).  prune != 0: residue pairs whose atom centroids are at least cutoff + 1e-6 apart are not
+ * evaluated (their mean atom distance cannot be below the cutoff), which changes no output.
+ *   deg [R] int32, mu_r_norm [R][5] fp32; edge_off [P + 1] int32: first edge of every protein and the total;
+ *   no_neighbor [P] int32: a protein's first residue (local index) without a neighbour under the cutoff, or -1;
+ *   n_pruned: one int32, the number of residue pairs i < j this call did not evaluate. */
+EQD_DOCK_API int eqd_dock_graph_select(int n_protein, const int32_t* res_off, const int32_t* prot_atom_off,
+                                       const float* atoms, const int32_t* atom_off, const double* x, double cutoff,
+                                       int max_neighbor, int prune, int32_t* deg, int32_t* edge_off, float* mu_r_norm,
+                                       int32_t* no_neighbor, int32_t* n_pruned, void* workspace, size_t ws_bytes,
+                                       void* stream);
+
+/* Enqueues the edge phase on a workspace eqd_dock_graph_select has filled: src / dst [E] int32 local to each protein,
+ * destination-major in the reference's neighbour order, he [E][27] fp32, all in protein order (E = edge_off[P]). */
+EQD_DOCK_API int eqd_dock_graph_edges(int n_protein, const int32_t* res_off, const int32_t* prot_atom_off,
+                                      int max_neighbor, const double* x, const double* n_i, const double* u_i,
+                                      const double* v_i, int32_t* src, int32_t* dst, float* he, void* workspace,
+                                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
