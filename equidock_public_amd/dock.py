@@ -3,10 +3,12 @@
     graphs of all complexes in one device pass (protein_graphs_batch)  ->  one batched eval forward per chunk
     ->  apply_rigid to each ligand's atoms
     ->  remove_clashes_batch: clash removal of ALL complexes in one device loop (libequidock_dock.so), each stopping on
-        its own  ->  PDB files and, with ground truth, the CRMSD / IRMSD summary
+        its own  ->  with ground truth: ligand / complex / interface RMSD of ALL complexes in one device pass
+        (rmsd_metrics_batch)  ->  PDB files and the CRMSD / IRMSD summary
 
 `remove_clashes_batch` is `inference.remove_clashes` for a list of complexes: same keys, same stop rule, same meaning;
-`dock_complexes` is the Python API, `python -m equidock_public_amd.dock` the command-line counterpart of
+`rmsd_metrics_batch` / `DeviceMeter` are `inference.rmsd_metrics` + `complex_and_interface_rmsd` /
+`inference.Meter_Unbound_Bound` for a list of complexes, results on the device; `dock_complexes` is the Python API, `python -m equidock_public_amd.dock` the command-line counterpart of
 inference_rigid.py.  There is no fallback: a missing libequidock_dock.so is an error.
 """
 import argparse
@@ -25,6 +27,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DOCK_LIB_PATH = os.path.join(HERE, 'libequidock_dock.so')
 DOCK_ABI_VERSION = 1
 DOCK_GRAPH_ABI = 1
+DOCK_METER_ABI = 1
+METER_COLS = 8             # EQD_DOCK_METER_COLS
 
 _dock = None
 _dock_is_sim = False
@@ -55,6 +59,14 @@ def _declare(lib):
     lib.eqd_dock_graph_edges.restype = C.c_int
     lib.eqd_dock_graph_edges.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_meter_abi.restype = C.c_int
+    lib.eqd_dock_meter_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_meter_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    lib.eqd_dock_meter_init.restype = C.c_int
+    lib.eqd_dock_meter_init.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_meter_eval.restype = C.c_int
+    lib.eqd_dock_meter_eval.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 
 
 def _bind(path):
@@ -65,6 +77,8 @@ def _bind(path):
         raise _lib.EquidockHipError(f"{path}: dock ABI version {lib.eqd_dock_abi_version()} != {DOCK_ABI_VERSION}")
     if lib.eqd_dock_graph_abi() != DOCK_GRAPH_ABI:
         raise _lib.EquidockHipError(f"{path}: dock graph ABI {lib.eqd_dock_graph_abi()} != {DOCK_GRAPH_ABI}")
+    if lib.eqd_dock_meter_abi() != DOCK_METER_ABI:
+        raise _lib.EquidockHipError(f"{path}: dock meter ABI {lib.eqd_dock_meter_abi()} != {DOCK_METER_ABI}")
     _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
     return lib
 
@@ -172,6 +186,142 @@ def remove_clashes_batch(ligand_atoms_list, receptor_atoms_list, sigma=8.0, surf
         out.append({'positions': pos, 'euler': euler, 'translation': trans, 'iterations': int(host[c].it),
                     'loss': float(host[c].loss)})
     return out
+
+
+# ---- batched RMSD meter -----------------------------------------------------------------------------------------------
+class MeterPlan:
+    """Workspace of eqd_dock_meter_eval for one set of host offsets: created and initialised once (init copies the item
+    table and waits for that copy), then `eval` only enqueues launches - it can be captured into a hipGraph."""
+
+    def __init__(self, lig_off, rec_off, dev):
+        lib = load_dock_library()
+        self.lig_off = np.ascontiguousarray(np.asarray(lig_off, dtype=np.int32))
+        self.rec_off = np.ascontiguousarray(np.asarray(rec_off, dtype=np.int32))
+        if len(self.lig_off) != len(self.rec_off) or len(self.lig_off) < 2:
+            raise ValueError(f"{len(self.lig_off)} ligand offsets for {len(self.rec_off)} receptor offsets")
+        self.n, self.dev = len(self.lig_off) - 1, torch.device(dev)
+        self._lo, self._ro = self.lig_off.ctypes.data_as(C.c_void_p), self.rec_off.ctypes.data_as(C.c_void_p)
+        self.wsb = lib.eqd_dock_meter_workspace_bytes(self.n, self._lo, self._ro)
+        if self.wsb == 0:
+            check(2)
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        with _lib.device_guard(self.dev):
+            check(lib.eqd_dock_meter_init(self.n, self._lo, self._ro, _lib.ptr(self.ws), C.c_size_t(self.wsb),
+                                          _stream(self.dev)))
+
+    def eval(self, lig_pred, rec_pred, lig_true, rec_true, out, cutoff=8.0, interface=True):
+        """Enqueue the metric pass on the current stream: [sum n][3] fp32 contiguous inputs (rec_pred may be None: it is
+        rec_true), out [C][8] fp64.  No synchronisation, no allocation, no copy."""
+        with _lib.device_guard(self.dev):
+            check(_dock.eqd_dock_meter_eval(self.n, self._lo, self._ro, _lib.ptr(lig_pred),
+                                            _lib.ptr(rec_pred) if rec_pred is not None else C.c_void_p(0),
+                                            _lib.ptr(lig_true), _lib.ptr(rec_true), C.c_double(float(cutoff)),
+                                            int(bool(interface)), _lib.ptr(out), _lib.ptr(self.ws), C.c_size_t(self.wsb),
+                                            _stream(self.dev)))
+        return out
+
+
+def _meter_rows(ts, what):
+    return [_require_device(x.detach().to(torch.float32).reshape(-1, 3).contiguous(), f'{what} {i}') for i, x in enumerate(ts)]
+
+
+def rmsd_metrics_batch(lig_pred_list, lig_true_list, rec_true_list, rec_pred_list=None, cutoff=8.0, interface=True):
+    """inference.rmsd_metrics and inference.complex_and_interface_rmsd for C complexes in one device pass
+    (eqd_dock_meter_*): per complex the ligand and receptor RMSD (no alignment), the complex RMSD after Kabsch
+    superposition of all rows, and - with `interface` - the interface RMSD over the pairs of the ground truth closer than
+    `cutoff` (NaN for a complex without such a pair) and their number.  `rec_pred_list` None: the receptor is its own
+    prediction, as in src/train.py:137-140.  fp64 on the device from the fp32 rows; a complex's row is bit-identical
+    alone, in any batch and from run to run.
+
+    Returns a dict of device float64 tensors [C]: ligand_rmsd, receptor_rmsd, complex_rmsd, interface_rmsd,
+    interface_pairs, flags (bit 0 / bit 1: the Kabsch of the complex / interface set took the reflection branch), and
+    `metrics`, the raw [C][8] buffer.  Apart from the item-table copy of the workspace's init, the call does not
+    synchronise and downloads nothing."""
+    ligs_p, ligs_t, recs_t = list(lig_pred_list), list(lig_true_list), list(rec_true_list)
+    recs_p = None if rec_pred_list is None else list(rec_pred_list)
+    n = len(ligs_p)
+    if not (n == len(ligs_t) == len(recs_t)) or (recs_p is not None and len(recs_p) != n):
+        raise ValueError(f"{n} predicted ligands for {len(ligs_t)} true ligands, {len(recs_t)} true receptors and "
+                         f"{'no' if recs_p is None else len(recs_p)} predicted receptors")
+    if n == 0:
+        raise ValueError("rmsd_metrics_batch: no complexes")
+    ligs_p, ligs_t, recs_t = _meter_rows(ligs_p, 'predicted ligand'), _meter_rows(ligs_t, 'true ligand'), _meter_rows(recs_t, 'true receptor')
+    if recs_p is not None:
+        recs_p = _meter_rows(recs_p, 'predicted receptor')
+    for c in range(n):
+        if ligs_p[c].shape[0] != ligs_t[c].shape[0]:
+            raise ValueError(f"complex {c}: {ligs_p[c].shape[0]} predicted ligand rows for {ligs_t[c].shape[0]} true ones")
+        if recs_p is not None and recs_p[c].shape[0] != recs_t[c].shape[0]:
+            raise ValueError(f"complex {c}: {recs_p[c].shape[0]} predicted receptor rows for {recs_t[c].shape[0]} true ones")
+    dev = ligs_p[0].device
+    plan = MeterPlan(_offsets([x.shape[0] for x in ligs_t]), _offsets([x.shape[0] for x in recs_t]), dev)
+    out = torch.empty(n, METER_COLS, dtype=torch.float64, device=dev)
+    plan.eval(torch.cat(ligs_p, 0), None if recs_p is None else torch.cat(recs_p, 0), torch.cat(ligs_t, 0),
+              torch.cat(recs_t, 0), out, cutoff=cutoff, interface=interface)
+    return {'ligand_rmsd': out[:, 0], 'receptor_rmsd': out[:, 1], 'complex_rmsd': out[:, 2], 'interface_rmsd': out[:, 3],
+            'interface_pairs': out[:, 4], 'flags': out[:, 5], 'metrics': out}
+
+
+class DeviceMeter:
+    """inference.Meter_Unbound_Bound (src/utils/eval.py:12-77, same method names) for whole batches: `update_batch`
+    appends the batch's metric rows on the device without synchronising, the summaries download the accumulated rows
+    once.  `interface`: also evaluate the interface RMSD (summarize_interface)."""
+
+    def __init__(self, cutoff=8.0, interface=False):
+        self.cutoff, self.interface = float(cutoff), bool(interface)
+        self._rows = []          # [C][8] device tensors
+
+    def __len__(self):
+        return sum(int(r.shape[0]) for r in self._rows)
+
+    def update_batch(self, lig_pred_list, rec_pred_list, lig_true_list, rec_true_list):
+        """One rmsd_metrics_batch over the lists (rec_pred_list may be None); returns the batch's complex RMSDs [C] on
+        the device."""
+        m = rmsd_metrics_batch(lig_pred_list, lig_true_list, rec_true_list, rec_pred_list, cutoff=self.cutoff,
+                               interface=self.interface)
+        self._rows.append(m['metrics'])
+        return m['complex_rmsd']
+
+    def update_rmsd(self, ligand_coors_pred, receptor_coors_pred, ligand_coors_true, receptor_coors_true):
+        """The host meter's signature: a batch of one (returns the complex RMSD as a device scalar)."""
+        return self.update_batch([ligand_coors_pred], [receptor_coors_pred], [ligand_coors_true], [receptor_coors_true])[0]
+
+    def append_rows(self, rows):
+        """Take a copy of a [C][8] metrics buffer the caller has filled (a device-to-device copy on the current stream)."""
+        if rows.dim() != 2 or rows.shape[1] != METER_COLS or rows.dtype != torch.float64:
+            raise ValueError(f"append_rows: expected a float64 [C][{METER_COLS}] buffer, got {rows.dtype} {tuple(rows.shape)}")
+        self._rows.append(rows.detach().clone())
+
+    def rows(self):
+        """The accumulated [N][8] rows on the host (ONE download)."""
+        if not self._rows:
+            return np.zeros((0, METER_COLS), dtype=np.float64)
+        return (self._rows[0] if len(self._rows) == 1 else torch.cat(self._rows, 0)).cpu().numpy()
+
+    @staticmethod
+    def _reduction(reduction_rmsd):
+        if reduction_rmsd not in ('mean', 'median'):
+            raise ValueError("Meter_Unbound_Bound: reduction_rmsd mis specified!")
+        return np.mean if reduction_rmsd == 'mean' else np.median
+
+    def summarize(self, reduction_rmsd='median'):
+        f = self._reduction(reduction_rmsd)
+        r = self.rows()
+        return f(r[:, 0]), f(r[:, 1]), f(r[:, 2])
+
+    def summarize_with_std(self, reduction_rmsd='median'):
+        f = self._reduction(reduction_rmsd)
+        arr = self.rows()[:, 2]
+        return f(arr), np.std(arr)
+
+    def summarize_interface(self, reduction_rmsd='median'):
+        """(reduced interface RMSD, its std) over the complexes that have an interface."""
+        f = self._reduction(reduction_rmsd)
+        arr = self.rows()[:, 3]
+        arr = arr[~np.isnan(arr)]
+        if arr.size == 0:
+            return float('nan'), float('nan')
+        return f(arr), np.std(arr)
 
 
 # ---- batched graph construction -------------------------------------------------------------------------------------
@@ -322,6 +472,51 @@ def _side(x):
     return list(x), FZ.atoms_ragged(list(x))[0]
 
 
+def _ca_index(x):
+    """Rows of the C-alpha atoms among the all-atom rows of `_side(x)`, by the rule of inference.read_pdb_atoms(ca_only=True)
+    (ATOM records whose name field reads CA, in file order)."""
+    if isinstance(x, (str, os.PathLike)):
+        with open(x) as f:
+            names = [line[12:16].strip() for line in f if line.startswith('ATOM')]
+    else:
+        names = [a.strip() for r in x for a in r.atom_names]
+    return np.nonzero(np.asarray(names) == 'CA')[0].astype(np.int64)
+
+
+def _ca_coords(x):
+    """C-alpha coordinates [n, 3] float32 of a PDB path or a residue list (same rule)."""
+    if isinstance(x, (str, os.PathLike)):
+        return INF.read_pdb_atoms(x, ca_only=True)
+    x = list(x)
+    return np.ascontiguousarray(FZ.atoms_ragged(x)[0][_ca_index(x)], dtype=np.float32).reshape(-1, 3)
+
+
+def _chunk_metrics(chunk, truths, first, final_lig, rec_atoms, cutoff, dev):
+    """The metrics stage of dock_complexes for one chunk: C-alpha rows of the final ligands and of the receptors taken on
+    the device by an index built on the host, one rmsd_metrics_batch, ONE download of the [C][8] rows."""
+    li, ri, gts = [], [], []
+    for k, ((lig_in, rec_in), gt) in enumerate(zip(chunk, truths)):
+        li.append(_ca_index(lig_in))
+        ri.append(_ca_index(rec_in))
+        gts.append(_ca_coords(gt))
+        if len(li[-1]) != len(gts[-1]) or len(li[-1]) == 0:
+            raise ValueError(f"complex {first + k}: the ligand has {len(li[-1])} C-alpha atoms, its ground truth {len(gts[-1])}")
+        if len(ri[-1]) == 0:
+            raise ValueError(f"complex {first + k}: the receptor has no C-alpha atom")
+    n_idx, n_gt = sum(len(a) for a in li + ri), sum(len(a) for a in gts)
+    hidx, hgt = _staging(n_idx, torch.int64, dev), _staging(3 * n_gt, torch.float32, dev)
+    hidx.numpy()[:] = np.concatenate(li + ri)
+    hgt.numpy()[:] = np.concatenate(gts, 0).reshape(-1)
+    didx, dgt = hidx.to(dev, non_blocking=True), hgt.to(dev, non_blocking=True).view(-1, 3)
+    ioff = np.concatenate([[0], np.cumsum([len(a) for a in li + ri])])
+    goff = np.concatenate([[0], np.cumsum([len(a) for a in gts])])
+    n = len(chunk)
+    lig_pred = [final_lig[k].index_select(0, didx[ioff[k]:ioff[k + 1]]) for k in range(n)]
+    rec_true = [rec_atoms[k].index_select(0, didx[ioff[n + k]:ioff[n + k + 1]]) for k in range(n)]
+    lig_true = [dgt[goff[k]:goff[k + 1]] for k in range(n)]
+    return rmsd_metrics_batch(lig_pred, lig_true, rec_true, cutoff=cutoff, interface=True)['metrics'].cpu().numpy()
+
+
 def _sync(dev):
     if dev.type == 'cuda':
         torch.cuda.synchronize(dev)
@@ -350,7 +545,7 @@ def _chunk_graphs(chunk, cutoff, max_neighbor, dev):
 
 def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=None, device=None, cutoff=30.0,
                    max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50,
-                   batched_graphs=True):
+                   batched_graphs=True, ground_truth=None, interface_cutoff=8.0):
     """Dock a list of (ligand, receptor) complexes, each side a PDB path or a list of featurize.Residue (the ligand's
     file / residues in their input pose, the receptor's in the bound pose - the reference's `*_l_b.pdb` and
     `*_r_b_COMPLEX.pdb`).  Per chunk of `max_complexes_per_batch` complexes (all at once by default): graphs on the
@@ -361,8 +556,18 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
     Returns one dict per complex: rotation [3, 3], translation [3] (numpy), ligand_atoms_docked (apply_rigid of all ligand
     atoms, before clash removal) and ligand_atoms (after it; the same tensor without clash removal), clash_iterations,
     clash_loss, n_ligand_atoms / n_receptor_atoms, and `batch_seconds`: wall times of the complex's chunk (graphs, model,
-    rigid, clashes, total; device-synchronised)."""
+    rigid, clashes, total; device-synchronised).
+
+    `ground_truth`: one entry per complex, the ligand in its bound pose (a PDB path or a list of featurize.Residue; the
+    receptor's ground truth is the receptor given).  Each chunk then ends with one rmsd_metrics_batch on the C-alpha rows
+    of its final ligands (taken on the device) and one download, and the results gain `crmsd`, `irmsd`, `ligand_rmsd`
+    (floats; irmsd NaN without a C-alpha pair closer than `interface_cutoff`) and `interface_pairs`; batch_seconds gains
+    'metrics'.  A ligand whose C-alpha count differs from its ground truth's raises ValueError.  Without it nothing changes."""
     complexes = list(complexes)
+    if ground_truth is not None:
+        ground_truth = list(ground_truth)
+        if len(ground_truth) != len(complexes):
+            raise ValueError(f"{len(ground_truth)} ground-truth ligands for {len(complexes)} complexes")
     dev = torch.device(device) if device is not None else next(net.parameters()).device
     step = len(complexes) if not max_complexes_per_batch else int(max_complexes_per_batch)
     results = []
@@ -406,6 +611,12 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
             t4 = time.perf_counter()
             times = {'graphs': t1 - t0, 'model': t2 - t1, 'rigid': t3 - t2, 'clashes': t4 - t3, 'total': t4 - t0,
                      'n_complexes': len(chunk)}
+            rows = None
+            if ground_truth is not None:
+                final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
+                rows = _chunk_metrics(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, interface_cutoff, dev)
+                t5 = time.perf_counter()           # (the download has synchronised)
+                times.update(metrics=t5 - t4, total=t5 - t0)
             for i in range(len(chunk)):
                 results.append({'rotation': rots[i].detach().cpu().numpy(), 'translation': trs[i].detach().cpu().numpy().reshape(3),
                                 'ligand_atoms_docked': docked[i],
@@ -414,6 +625,9 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                                 'clash_loss': cl[i]['loss'] if cl[i] is not None else None,
                                 'n_ligand_atoms': int(lig_atoms[i].shape[0]), 'n_receptor_atoms': int(rec_atoms[i].shape[0]),
                                 'batch_seconds': times})
+                if rows is not None:
+                    results[-1].update(crmsd=float(rows[i, 2]), irmsd=float(rows[i, 3]), ligand_rmsd=float(rows[i, 0]),
+                                       interface_pairs=int(rows[i, 4]))
     finally:
         net.train(was_training)
     return results
@@ -440,6 +654,9 @@ def main(argv=None):
     p.add_argument('--device', default='cuda:0')
     p.add_argument('--no-batched-graphs', action='store_true',
                    help='build the graphs in a loop over the complexes instead of one device pass per batch (same results)')
+    p.add_argument('--device-metrics', action='store_true',
+                   help='CRMSD / IRMSD of every complex from one batched device pass per batch on the docked C-alpha atoms '
+                        '(needs every <name>_l_b_COMPLEX.pdb) instead of re-reading the written files on the host')
     a = p.parse_args(argv)
     try:
         names = sorted(os.path.basename(f)[:-len('_l_b.pdb')] for f in glob.glob(os.path.join(a.input_dir, '*_l_b.pdb')))
@@ -451,6 +668,12 @@ def main(argv=None):
             if not os.path.isfile(rec):
                 raise FileNotFoundError(f"{rec} is missing (receptor of {nm})")
             complexes.append((os.path.join(a.input_dir, nm + '_l_b.pdb'), rec))
+        truths = None
+        if a.device_metrics:
+            truths = [os.path.join(a.gt_dir, nm + '_l_b_COMPLEX.pdb') for nm in names]
+            for gt in truths:
+                if not os.path.isfile(gt):
+                    raise FileNotFoundError(f"{gt} is missing (--device-metrics needs the ground-truth ligand of every complex)")
         os.makedirs(a.out_dir, exist_ok=True)
         dev = torch.device(a.device)
         net = load_checkpoint(a.checkpoint, dev)
@@ -459,7 +682,7 @@ def main(argv=None):
         res = dock_complexes(net, complexes, remove_clashes=a.remove_clashes, max_complexes_per_batch=a.batch or None,
                              device=dev, cutoff=float(ca.get('graph_cutoff', 30.0)),
                              max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it,
-                             batched_graphs=not a.no_batched_graphs)
+                             batched_graphs=not a.no_batched_graphs, ground_truth=truths)
         suffix = '_EQUIDOCK_NO_CLASHES.pdb' if a.remove_clashes else '_EQUIDOCK.pdb'
         crmsd, irmsd = [], []
         for nm, (lig_path, rec_path), r in zip(names, complexes, res):
@@ -469,7 +692,11 @@ def main(argv=None):
             if a.remove_clashes:
                 line += f"  clash iterations {r['clash_iterations']}, loss {r['clash_loss']:.4f}"
             gt = os.path.join(a.gt_dir, nm + '_l_b_COMPLEX.pdb')
-            if os.path.isfile(gt):
+            if a.device_metrics:
+                crmsd.append(r['crmsd'])
+                irmsd.append(r['irmsd'])
+                line += f"  CRMSD {r['crmsd']:.3f}  IRMSD {r['irmsd']:.3f}"
+            elif os.path.isfile(gt):
                 rec_ca = INF.read_pdb_atoms(rec_path, ca_only=True)
                 c, i = INF.complex_and_interface_rmsd(INF.read_pdb_atoms(out, ca_only=True), rec_ca,
                                                       INF.read_pdb_atoms(gt, ca_only=True), rec_ca)

@@ -17,6 +17,13 @@ this round trip is the only host join and everything around it replays from hipG
 `step()` returns the loss tensor; `last_ot_exposed_ms()` is the stretch of the GPU timeline between the end of graph M and the
 start of graph B - what the host solve and its two copies cost the step.  `step_eager()` is the same arithmetic through the
 autograd wrappers of losses.py (what tests compare with the oracle).  No CPU fallback: tensors must be on the GPU.
+
+`TrainStep(meter=dock.DeviceMeter())` also meters the step: graph M evaluates the ligand / receptor / complex RMSD of every
+pair (eqd_dock_meter_eval on the forward's ligand output against lig_target, the receptor its own prediction as in
+src/train.py:137-140, no interface) into a fixed [B][8] buffer, and every step() / step_unfused() ends with a
+device-to-device copy of that buffer into the meter - no further host join.  One difference from the reference: it samples
+a random tenth of the training pairs (src/train.py:136), this meters every pair of every step it is attached to; the
+caller attaches the meter (an evaluation epoch, a sampled training step) or not.  Without `meter` nothing new is launched.
 """
 import ctypes as C
 
@@ -28,11 +35,12 @@ from . import _lib, losses
 class TrainStep:
 
     def __init__(self, net, batch, lig_target, rec, pocket_lig_list, pocket_rec_list, w_ot=1.0, w_int=10.0, sigma=25.0,
-                 surface_ct=10.0, reducer=None, n_threads=0, allreduce=False):
+                 surface_ct=10.0, reducer=None, n_threads=0, allreduce=False, meter=None):
         """lig_target [n_lig, 3] / rec [n_rec, 3]: bound coordinates in the batch's node order (src/train.py:114, 131);
         pocket_*_list: per pair (n_pocket, 3), matched rows; weights / sigma / surface_ct: src/utils/args.py:64-70;
         reducer: parallel.FlatGradAllReduce of `net` (gradients accumulate in its flat buffer); allreduce: issue the
-        collective at the end of the backward (a process group must exist)."""
+        collective at the end of the backward (a process group must exist); meter: a dock.DeviceMeter that receives the
+        [B][8] RMSD rows of every step (see the module docstring)."""
         from .parallel import FlatGradAllReduce
         self.net, self.batch = net, batch
         self.packed = batch.pack()
@@ -76,6 +84,11 @@ class TrainStep:
         self._outs = None
         self._ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if dev.type == 'cuda' else None
         self._exposed = []
+        self.meter, self._meter_muted = meter, False
+        if meter is not None:       # workspace and item table now, outside any capture
+            from . import dock
+            self._meter_plan = dock.MeterPlan(self.packed.lig_off.cpu().numpy(), self.packed.rec_off.cpu().numpy(), dev)
+            self.meter_rows = torch.zeros(B, dock.METER_COLS, dtype=torch.float64, device=dev)
 
     # ---- the pieces (each enqueues on the current stream; none synchronises) -------------------------------------------
     def _forward_and_cost(self):
@@ -101,6 +114,8 @@ class TrainStep:
             _lib.check(lib.eqd_pair_losses_bwd(C.byref(gs), _lib.ptr(lig), _lib.ptr(self.lig_target), _lib.ptr(self.rec),
                                                C.c_float(self.sigma), C.c_float(self.ct), _lib.ptr(self.s_lig), _lib.ptr(self.s_rec),
                                                _lib.ptr(self.d_mse), _lib.ptr(self.d_inter), _lib.ptr(self.d_lig), st))
+        if self.meter is not None:
+            self._meter_plan.eval(lig, None, self.lig_target, self.rec, self.meter_rows, interface=False)
 
     def _solve_on_host(self):
         """exact plans of the B transport problems, pinned buffer to pinned buffer (the caller has waited for the cost copy)"""
@@ -137,6 +152,7 @@ class TrainStep:
             self._solve_on_host()
             self.plan.copy_(self.plan_host)
             bwd()
+            self._metered()
             return self.loss
         cur = torch.cuda.current_stream(self.dev)
         copied = torch.cuda.Event()
@@ -149,7 +165,12 @@ class TrainStep:
         self.plan.copy_(self.plan_host, non_blocking=True)
         self._ev[1].record(cur)
         bwd()
+        self._metered()
         return self.loss
+
+    def _metered(self):
+        if self.meter is not None and not self._meter_muted:
+            self.meter.append_rows(self.meter_rows)
 
     def step_unfused(self):
         """the same step with every launch enqueued from the host (no graphs)"""
@@ -161,9 +182,11 @@ class TrainStep:
         torch.cuda.synchronize()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
+        self._meter_muted = True                  # (the warm-up steps are not the caller's)
         with torch.cuda.stream(side):
             for _ in range(2):
                 self.step_unfused()
+        self._meter_muted = False
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         gf, gm, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()

@@ -106,6 +106,43 @@ EQD_DOCK_API int eqd_dock_graph_edges(int n_protein, const int32_t* res_off, con
                                       const double* v_i, int32_t* src, int32_t* dst, float* he, void* workspace,
                                       size_t ws_bytes, void* stream);
 
+/*
+ * Batched RMSD meter: Meter_Unbound_Bound.update_rmsd (src/utils/eval.py:12-36) and the CRMSD / IRMSD of
+ * src/test_all_methods/eval_pdb_outputset.py:80-100 for C complexes in one device pass.  fp64 arithmetic from the fp32
+ * inputs; a complex's row of results is bit-identical alone, in any batch, at any position and from run to run.
+ *
+ * Layout: the complexes are stored one after another, as above.
+ *   lig_pred, lig_true [sum n_l][3] fp32, rec_pred, rec_true [sum n_r][3] fp32 (rec_pred may be NULL: it is rec_true)
+ *   lig_off / rec_off [C + 1]  HOST int32, starting at 0, every complex >= 1 row on each side
+ *   metrics [C][EQD_DOCK_METER_COLS] fp64:
+ *     0 ligand RMSD, 1 receptor RMSD (no alignment), 2 complex RMSD (after Kabsch superposition of all rows),
+ *     3 interface RMSD: Kabsch RMSD over the pairs (i, j) with |lig_true_i - rec_true_j| < cutoff, a row once per
+ *       partner; NaN without such a pair and when interface == 0,
+ *     4 the number of interface pairs, 5 flags (bit 0: the complex set took the reflection branch det(V U^T) < 0,
+ *       bit 1: the interface set did), 6 and 7: 0
+ * Sequence: workspace_bytes -> init (once per set of offsets) -> eval (any number of times).
+ */
+#define EQD_DOCK_METER_ABI 1
+#define EQD_DOCK_METER_COLS 8
+EQD_DOCK_API int eqd_dock_meter_abi(void);
+
+/* Workspace of a batch with these host offsets; 0 when they are invalid or do not fit 32-bit offsets
+ * (eqd_dock_last_error says why). */
+EQD_DOCK_API size_t eqd_dock_meter_workspace_bytes(int n_complex, const int32_t* lig_off, const int32_t* rec_off);
+
+/* Validates the offsets and writes the batch's work-item table into the workspace (a host-to-device copy; this call
+ * waits for that copy). */
+EQD_DOCK_API int eqd_dock_meter_init(int n_complex, const int32_t* lig_off, const int32_t* rec_off, void* workspace,
+                                     size_t ws_bytes, void* stream);
+
+/* Enqueues the metric pass (five launches, four when interface == 0, whatever C is) on a workspace prepared by
+ * eqd_dock_meter_init with the same offsets.  No synchronisation, no allocation, no host-device copy: the call can be
+ * captured into a hipGraph.  cutoff must be finite and > 0. */
+EQD_DOCK_API int eqd_dock_meter_eval(int n_complex, const int32_t* lig_off, const int32_t* rec_off,
+                                     const float* lig_pred, const float* rec_pred, const float* lig_true,
+                                     const float* rec_true, double cutoff, int interface, double* metrics,
+                                     void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
