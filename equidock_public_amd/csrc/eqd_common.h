@@ -136,6 +136,7 @@ __device__ __forceinline__ void glds16(const float* gsrc, float* lds_base) {
 template <int N>
 __device__ __forceinline__ void vm_wait() { static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit count"); }
 __device__ __forceinline__ void lds_barrier() { __syncthreads(); }
+__device__ __forceinline__ void lds_reads_done() {}
 template <class T>
 __device__ __forceinline__ void keep_after_wait(T&) {}
 #else
@@ -161,6 +162,9 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
+// every LDS read this wave has issued has returned: a copy into the same bytes may be requested (nothing else orders an
+// LDS-DMA write behind an earlier ds_read of the wave that issues it)
+__device__ __forceinline__ void lds_reads_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 template <class T>
 __device__ __forceinline__ void keep_after_wait(T& v) { asm volatile("" : "+v"(v)); }
 #endif

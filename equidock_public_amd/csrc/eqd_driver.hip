@@ -203,6 +203,75 @@ EqdAtbJob atb_job(const float* X, int ldx, int M, const float* Y, int ldy, int N
     return J;
 }
 
+// The backward row chain of one layer, as eqd_model_backward launches it: [dh of the layer above (kept as LDS tile 2) ->]
+// da1n = alpha dH Wn2 (tile 0) -> LeakyReLU / LayerNorm backward (dz, tile 1, the ln_part rows) -> dz times the column
+// blocks of Wn1: d aggr_msg, d aggr_cross (cross messages only), the embedding columns of d h0 accumulated over the layers.
+// Returns the number of jobs written to cj (<= 6).  (Also built by eqd_selftest_node_chain_bwd: the same lists on test buffers.)
+struct NodeBwdChain {
+    int N, d, da, d0, d_emb, ldn, dh_width;
+    float slope, eps, alpha;
+    bool cross;
+    const EqdLinJob* dh;      // the dh job of the layer above, or NULL: the last layer, which also initialises dh0acc
+    const float *dHout, *Wn2, *Wn1, *y_act, *ln_g, *drop_mul;
+    float *dz, *lnp, *d_aggr_msg, *d_aggr_cross, *dh0acc;
+};
+int node_bwd_chain(const NodeBwdChain& c, EqdChainJob* cj) {
+    int nj = 0;
+    auto clear = [&](EqdChainJob& C) {
+        memset(&C, 0, sizeof(C));
+        for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
+        C.out_local = -1;
+    };
+    const bool fused_dh = c.dh != nullptr;
+    if (fused_dh) {
+        EqdChainJob& C = cj[nj++];
+        clear(C);
+        C.lin = *c.dh;
+        C.out_local = 2;
+    }
+    {
+        EqdChainJob& C = cj[nj++];
+        clear(C);
+        C.lin = lin_job(c.N, c.d, nullptr, c.d, c.slope, c.eps);
+        lin_src(C.lin, 0, c.dHout, c.dh_width, c.dh_width, c.Wn2, 1, c.d);
+        C.lin.nsrc = 1; C.lin.alpha = c.alpha;
+        if (fused_dh) C.src_local[0] = 2;
+        C.out_local = 0;
+    }
+    {
+        EqdChainJob& C = cj[nj++];
+        clear(C);
+        C.type = 1;
+        C.lin = lin_job(c.N, c.d, c.dz, c.d, c.slope, c.eps);
+        lin_src(C.lin, 0, c.y_act, c.d, c.d, nullptr, 0, 0);
+        C.lin.nsrc = 1; C.lin.ln_g = c.ln_g;
+        C.lin.mul = c.drop_mul; C.lin.ld_mul = c.d;
+        C.src_local[0] = 0;
+        C.out_local = 1;
+        C.aux = c.lnp;
+    }
+    auto dx_job = [&](float* Y, int M, int ldy, int coff) -> EqdChainJob& {
+        EqdChainJob& C = cj[nj++];
+        clear(C);
+        C.lin = lin_job(c.N, M, Y, ldy, c.slope, c.eps);
+        lin_src(C.lin, 0, c.dz, c.d, c.d, c.Wn1 + coff, 1, c.ldn);
+        C.lin.nsrc = 1;
+        C.src_local[0] = 1;
+        return C;
+    };
+    dx_job(c.d_aggr_msg, 64, 64, c.d);
+    // (padding columns of d aggr_cross when da != d: the job writes them as zeros, EqdLinJob.pad_to - they meet zeros in V,
+    //  but must not be NaN bit patterns left in the scratch buffer)
+    if (c.cross) dx_job(c.d_aggr_cross, c.d, c.da, c.d + 64).lin.pad_to = c.da != c.d ? c.da : 0;
+    // only the embedding columns of d h0 are ever read (k_embed_bwd: the trailing node features are inputs), so the
+    // job computes d_emb of the d0 columns: a 64-wide job instead of a 69-wide one (the general body)
+    EqdChainJob& C5 = dx_job(c.dh0acc, c.d_emb, c.d0, 2 * c.d + 64);
+    if (fused_dh) {      // the last layer (processed first) initialises the accumulator
+        C5.lin.R = c.dh0acc; C5.lin.ldr = c.d0; C5.lin.beta = 1.f;
+    }
+    return nj;
+}
+
 // node-level weight-gradient jobs of one layer (also used with NULL pointers for sizing)
 int node_atb_jobs(const Dims& D, int l, const EqdModelDesc* m, const Saved* S, const float* dHout, const float* dz,
                   const float* dP, const float* dQ, const float* dq, const float* dk, const float* dv,
@@ -1002,58 +1071,18 @@ extern "C" int eqd_model_backward(const EqdModelDesc* m, const EqdGraph* g, cons
         // d aggr_msg, d aggr_cross, d h0
         {
             EqdChainJob cj[8];
-            int nj = 0;
-            auto clear = [&](EqdChainJob& C) {
-                memset(&C, 0, sizeof(C));
-                for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
-                C.out_local = -1;
-            };
-            const bool fused_dh = l < D.L - 1;
-            if (l < D.L - 1) {
-                EqdChainJob& C = cj[nj++];
-                clear(C);
-                C.lin = dh_job(l + 1);
-                C.out_local = 2;
-            }
-            {
-                EqdChainJob& C = cj[nj++];
-                clear(C);
-                C.lin = lin_job(N, d, nullptr, d, slope, eps);
-                lin_src(C.lin, 0, dHout, D.dh, D.dh, p[P_WN2], 1, d);
-                C.lin.nsrc = 1; C.lin.alpha = alpha;
-                if (fused_dh) C.src_local[0] = 2;
-                C.out_local = 0;
-            }
             float* lnp = W.ln_part + (size_t)l * W.ln_part_stride;
-            {
-                EqdChainJob& C = cj[nj++];
-                clear(C);
-                C.type = 1;
-                C.lin = lin_job(N, d, dz, d, slope, eps);
-                lin_src(C.lin, 0, Ls.y_act, d, d, nullptr, 0, 0);
-                C.lin.nsrc = 1; C.lin.ln_g = p[P_NLG];
-                C.lin.mul = drop_node(D, drop, l); C.lin.ld_mul = d;
-                C.src_local[0] = 0;
-                C.out_local = 1;
-                C.aux = lnp;
-            }
-            auto dx_job = [&](float* Y, int M, int ldy, int coff) -> EqdChainJob& {
-                EqdChainJob& C = cj[nj++];
-                clear(C);
-                C.lin = lin_job(N, M, Y, ldy, slope, eps);
-                lin_src(C.lin, 0, dz, d, d, p[P_WN1] + coff, 1, ldn);
-                C.lin.nsrc = 1;
-                C.src_local[0] = 1;
-                return C;
-            };
-            dx_job(W.d_aggr_msg, 64, 64, d);
-            if (m->cross_msgs) dx_job(W.d_aggr_cross, d, da, d + 64).lin.pad_to = da != d ? da : 0;
-            // only the embedding columns of d h0 are ever read (k_embed_bwd: the trailing node features are inputs), so the
-            // job computes m->d_emb of the D.d0 columns: a 64-wide job instead of a 69-wide one (the general body)
-            EqdChainJob& C5 = dx_job(W.dh0acc, m->d_emb, D.d0, 2 * d + 64);
-            if (l < D.L - 1) {      // the last layer (processed first) initialises the accumulator
-                C5.lin.R = W.dh0acc; C5.lin.ldr = D.d0; C5.lin.beta = 1.f;
-            }
+            EqdLinJob dhj;
+            if (l < D.L - 1) dhj = dh_job(l + 1);
+            NodeBwdChain nc;
+            nc.N = N; nc.d = d; nc.da = da; nc.d0 = D.d0; nc.d_emb = m->d_emb; nc.ldn = ldn; nc.dh_width = D.dh;
+            nc.slope = slope; nc.eps = eps; nc.alpha = alpha;
+            nc.cross = m->cross_msgs != 0;
+            nc.dh = l < D.L - 1 ? &dhj : nullptr;
+            nc.dHout = dHout; nc.Wn2 = p[P_WN2]; nc.Wn1 = p[P_WN1]; nc.y_act = Ls.y_act; nc.ln_g = p[P_NLG];
+            nc.drop_mul = drop_node(D, drop, l);
+            nc.dz = dz; nc.lnp = lnp; nc.d_aggr_msg = W.d_aggr_msg; nc.d_aggr_cross = W.d_aggr_cross; nc.dh0acc = W.dh0acc;
+            const int nj = node_bwd_chain(nc, cj);
             int nb = 0;      // partial rows of the LayerNorm-backward sums = workgroups of whichever kernel took the chain
             RC(eqd_launch_rowchain(cj, nj, N, st, &nb));
             if (defer->n + 2 <= 512) {
@@ -1294,4 +1323,45 @@ extern "C" int eqd_node_update_bwd(int rows, const EqdNodeUpdateParams* p, const
     int na = 0;
     node_update_atb_jobs(rows, p, h, aggr_msg, aggr_cross, h0, a1n, d_h_out, W.dz, grads, jobs, &na);
     return eqd_atb(jobs, na, W.atb_part, W.atb_bytes, st);
+}
+
+// Test aid: the backward row chain of one 64-wide layer on the caller's buffers, through the list builder eqd_model_backward
+// uses (node_bwd_chain) - so that a test can put guard rows behind dz, the ln_part rows, d aggr_msg, d aggr_cross and dh0acc,
+// which the model keeps inside its scratch arena.
+extern "C" int eqd_selftest_node_chain_bwd(const EqdNodeChainBwdTest* t, int* partial_rows, void* stream) {
+    if (!t || !partial_rows || !t->dH_above || !t->Wn2 || !t->Wn1 || !t->y_act || !t->ln_g || !t->dz || !t->ln_part ||
+        !t->d_aggr_msg || !t->d_aggr_cross || !t->dh0acc || (t->with_dh && !t->dH)) {
+        eqd_set_error("eqd_selftest_node_chain_bwd: NULL argument");
+        return EQD_ERR_NULL;
+    }
+    if (t->rows <= 0 || t->d0 < 64 || t->d0 > 80) {
+        eqd_set_error("eqd_selftest_node_chain_bwd: rows=%d d0=%d", t->rows, t->d0);
+        return EQD_ERR_SHAPE;
+    }
+    g_bf16_mode = 0;
+    const int d = 64;
+    EqdLinJob dhj;
+    if (t->with_dh) {      // (dh_job of eqd_model_backward at a 64-wide layer with cross messages)
+        dhj = lin_job(t->rows, d, t->dH, d, t->slope, t->ln_eps);
+        for (int s = 0; s < 6; ++s) {
+            if (!t->dh_X[s] || !t->dh_W[s]) {
+                eqd_set_error("eqd_selftest_node_chain_bwd: NULL dh source %d", s);
+                return EQD_ERR_NULL;
+            }
+            lin_src(dhj, s, t->dh_X[s], d, d, t->dh_W[s], 1, t->dh_wcs[s]);
+        }
+        dhj.nsrc = 6;
+        dhj.R = t->dH_above; dhj.ldr = d; dhj.beta = 1.f - t->skip_weight_h;
+    }
+    NodeBwdChain nc;
+    nc.N = t->rows; nc.d = d; nc.da = d; nc.d0 = t->d0; nc.d_emb = 64; nc.ldn = t->d0 + 2 * d + 64; nc.dh_width = d;
+    nc.slope = t->slope; nc.eps = t->ln_eps; nc.alpha = t->skip_weight_h;
+    nc.cross = true;
+    nc.dh = t->with_dh ? &dhj : nullptr;
+    nc.dHout = t->with_dh ? t->dH : t->dH_above;
+    nc.Wn2 = t->Wn2; nc.Wn1 = t->Wn1; nc.y_act = t->y_act; nc.ln_g = t->ln_g; nc.drop_mul = t->drop_mul;
+    nc.dz = t->dz; nc.lnp = t->ln_part; nc.d_aggr_msg = t->d_aggr_msg; nc.d_aggr_cross = t->d_aggr_cross; nc.dh0acc = t->dh0acc;
+    EqdChainJob cj[8];
+    const int nj = node_bwd_chain(nc, cj);
+    return eqd_launch_rowchain(cj, nj, t->rows, (hipStream_t)stream, partial_rows);
 }

@@ -547,28 +547,24 @@ static int linear_row_tiles(int rows) {
 // waves through LDS - three rounds (mean; variance; the two projections) instead of the 16 six-step wave reductions per
 // wave of the one-wave-per-row layout, which ran one after the other (9 800 of the chain's 47 600 clocks).  yp: the
 // job's y_act values, fetched by the caller before the previous job (have_y) or here.
-__device__ __forceinline__ void chain_lnbwd64(const JobW& W, float (*Lb)[LIN_LOCALS][16 * LIN_S], float (*stat)[EQD_WAVES][16],
-                                              int row0, bool have_y, f32x4 yp) {
-#define LJ(f) JW_OFF(EqdLinJob, f)
+// J: where the job's operands come from - LnBwd64Desc (the descriptor words of a chain job, k_rowchain) or the preloaded
+// values of k_rowchain_res_bwd (eqd_chainres_bwd_inl.h); the arithmetic is this one function for both.
+template <class JOB>
+__device__ __forceinline__ void chain_lnbwd64_t(const JOB& J, float (*Lb)[LIN_LOCALS][16 * LIN_S], float (*stat)[EQD_WAVES][16],
+                                                int row0) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l15 = lane & 15, g = lane >> 4;
-    const int rows = jw_i(W, LJ(rows));
-    const int src_l = jw_i(W, JW_OFF(EqdChainJob, src_local)), out_l = jw_i(W, JW_OFF(EqdChainJob, out_local));
-    const float slope = jw_f(W, LJ(slope)), ln_eps = jw_f(W, LJ(ln_eps));
+    const int rows = J.rows();
+    const int src_l = J.src_l(), out_l = J.out_l();
+    const float slope = J.slope(), ln_eps = J.ln_eps();
     const int f0 = 16 * wave + 4 * g;
     const int rowi = row0 + l15;
     const bool rv = rowi < rows;
-    const f32x4 gam = *(const EQD_GAS f4v*)(jw_p<const float>(W, LJ(ln_g)) + f0);
-    if (!have_y) {
-        const int ldx = jw_i(W, LJ(s) + JW_OFF(EqdLinSrc, ldx));
-        yp = *(const EQD_GAS f4v*)(jw_p<const float>(W, LJ(s) + JW_OFF(EqdLinSrc, X)) + (size_t)(rv ? rowi : rows - 1) * ldx + f0);
-    }
-    float* const jY = jw_p<float>(W, LJ(Y));
-    const int ldy = jw_i(W, LJ(ldy));
-    float* const jaux = jw_p<float>(W, JW_OFF(EqdChainJob, aux));
-    f32x4 mulv = {1.f, 1.f, 1.f, 1.f};       // dropout factors of the forward (training mode): d LeakyReLU * keep * s
-    if (const float* const jmul = jw_p<const float>(W, LJ(mul)))
-        mulv = *(const EQD_GAS f4v*)(jmul + (size_t)(rv ? rowi : rows - 1) * jw_i(W, LJ(ld_mul)) + f0);
-#undef LJ
+    const f32x4 gam = J.gam(f0);
+    const f32x4 yp = J.y_act(rv ? rowi : rows - 1, f0);
+    float* const jY = J.Y();
+    const int ldy = J.ldy();
+    float* const jaux = J.aux();
+    const f32x4 mulv = J.mul(rv ? rowi : rows - 1, f0);      // dropout factors of the forward (training mode): d LeakyReLU * keep * s
     f32x4 o = *(const f32x4*)&Lb[0][src_l][l15 * LIN_S + f0];
     f32x4 y = yp;
     if (!rv) {
@@ -630,6 +626,39 @@ __device__ __forceinline__ void chain_lnbwd64(const JobW& W, float (*Lb)[LIN_LOC
     }
     // (the workgroup's partial row is [d gamma 0..127 | d beta 128..255]; columns of features >= 64 are never read)
 }
+struct LnBwd64Desc {      // the job as k_rowchain has it: descriptor words, y_act possibly fetched a job early
+    const JobW& W;
+    bool have_y;
+    f32x4 yp;
+#define LJ(f) JW_OFF(EqdLinJob, f)
+    __device__ __forceinline__ int rows() const { return jw_i(W, LJ(rows)); }
+    __device__ __forceinline__ int src_l() const { return jw_i(W, JW_OFF(EqdChainJob, src_local)); }
+    __device__ __forceinline__ int out_l() const { return jw_i(W, JW_OFF(EqdChainJob, out_local)); }
+    __device__ __forceinline__ float slope() const { return jw_f(W, LJ(slope)); }
+    __device__ __forceinline__ float ln_eps() const { return jw_f(W, LJ(ln_eps)); }
+    __device__ __forceinline__ f32x4 gam(int f0) const { return *(const EQD_GAS f4v*)(jw_p<const float>(W, LJ(ln_g)) + f0); }
+    __device__ __forceinline__ f32x4 y_act(int row, int f0) const {
+        if (have_y) return yp;
+        const int ldx = jw_i(W, LJ(s) + JW_OFF(EqdLinSrc, ldx));
+        return *(const EQD_GAS f4v*)(jw_p<const float>(W, LJ(s) + JW_OFF(EqdLinSrc, X)) + (size_t)row * ldx + f0);
+    }
+    __device__ __forceinline__ float* Y() const { return jw_p<float>(W, LJ(Y)); }
+    __device__ __forceinline__ int ldy() const { return jw_i(W, LJ(ldy)); }
+    __device__ __forceinline__ float* aux() const { return jw_p<float>(W, JW_OFF(EqdChainJob, aux)); }
+    __device__ __forceinline__ f32x4 mul(int row, int f0) const {
+        f32x4 mulv = {1.f, 1.f, 1.f, 1.f};
+        if (const float* const jmul = jw_p<const float>(W, LJ(mul)))
+            mulv = *(const EQD_GAS f4v*)(jmul + (size_t)row * jw_i(W, LJ(ld_mul)) + f0);
+        return mulv;
+    }
+#undef LJ
+};
+__device__ __forceinline__ void chain_lnbwd64(const JobW& W, float (*Lb)[LIN_LOCALS][16 * LIN_S], float (*stat)[EQD_WAVES][16],
+                                              int row0, bool have_y, f32x4 yp) {
+    chain_lnbwd64_t(LnBwd64Desc{W, have_y, yp}, Lb, stat, row0);
+}
+// k_rowchain_res_bwd: the resident-weights body of the backward chain (calls chain_lnbwd64_t)
+#include "eqd_chainres_bwd_inl.h"
 
 template <int RT>
 __device__ __forceinline__ void chain_lnbwd(const EqdChainJob& C, float (*Lb)[LIN_LOCALS][16 * LIN_S], float (*red)[256],
@@ -1005,6 +1034,80 @@ static std::atomic<long long> g_chain_resident_launches{0};
 // how many row chains this process has launched on the resident-weights body (tests: which body ran)
 extern "C" long long eqd_chain_resident_launches(void) { return g_chain_resident_launches.load(); }
 
+// k_rowchain_res_bwd (eqd_chainres_bwd_inl.h): the backward chain of a 64-wide layer under the same conditions.  Taken for
+// exactly the two job lists eqd_model_backward builds with cross_msgs on - [dh of the layer above,] alpha dH Wn2, LayerNorm
+// backward, dz times three ADJACENT 64-column blocks of Wn1 - matched structurally; crb_pack fills the kernel's compact
+// argument while it checks.  eqd_node_update_bwd's list (four column blocks in another order, a residual on the last
+// block of a five-job list) stays on k_rowchain.  EQD_CHAIN_RESIDENT=0 turns off both resident bodies,
+// EQD_CHAIN_RESIDENT_BWD=0 this one alone.
+static int chain_resident_bwd_on() {
+    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT_BWD");
+    return chain_resident_on() && !(f && f[0] == '0' && f[1] == 0);
+}
+static bool crb_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResBwdArg& A) {
+    if (!chain_resident_bwd_on() || (njobs != 5 && njobs != 6) || rows <= 0 || eqd_row_tiles(rows) != 1 ||
+        eqd_rowchain_blocks(rows) > eqd_num_cus())
+        return false;
+    const bool dh = njobs == 6;
+    // a linear job of this chain: 64 outputs, fp32, transposed 64-deep weight sources, none of the optional epilogue parts
+    auto plain = [&](const EqdChainJob& C, int nsrc) {
+        const EqdLinJob& J = C.lin;
+        if (C.type != 0 || J.bf16 || J.rows != rows || J.M != 64 || J.nsrc != nsrc || J.act || J.bias || J.ln_g || J.ln_b ||
+            J.pre_ln || J.mul || J.pad_to != 0 || J.Yb)
+            return false;
+        for (int s = 0; s < nsrc; ++s)
+            if (!J.s[s].W || J.s[s].mask || J.s[s].K != 64 || J.s[s].w_rs != 1) return false;
+        return true;
+    };
+    auto src = [](const EqdLinSrc& S) { return CrbSrc{S.X, S.W, S.ldx, S.w_cs}; };
+    auto out = [](const EqdLinJob& J) { return CrbOut{J.Y, J.R, J.ldy, J.ldr, J.alpha, J.beta}; };
+    memset(&A, 0, sizeof(A));
+    A.rows = rows;
+    int at = 0;
+    if (dh) {
+        const EqdChainJob& C = jobs[at++];
+        if (!plain(C, 6) || C.out_local != 2 || !C.lin.Y || !C.lin.R) return false;
+        for (int s = 0; s < 6; ++s) {
+            if (!C.lin.s[s].X || C.src_local[s] >= 0) return false;
+            A.dh[s] = src(C.lin.s[s]);
+        }
+        A.dho = out(C.lin);
+    }
+    {
+        const EqdChainJob& C = jobs[at++];
+        if (!plain(C, 1) || C.out_local != 0 || C.lin.Y || C.lin.R) return false;
+        if (dh ? C.src_local[0] != 2 : (C.src_local[0] >= 0 || !C.lin.s[0].X)) return false;
+        A.a = src(C.lin.s[0]);
+        A.a_alpha = C.lin.alpha;
+        A.a_beta = C.lin.beta;
+    }
+    {
+        const EqdChainJob& C = jobs[at++];
+        const EqdLinJob& J = C.lin;
+        if (C.type != 1 || J.bf16 || J.rows != rows || J.M != 64 || C.src_local[0] != 0 || C.out_local != 1 || !J.s[0].X ||
+            !J.ln_g || !J.Y || !C.aux)
+            return false;
+        A.y_act = J.s[0].X; A.ld_y = J.s[0].ldx;
+        A.ln_g = J.ln_g;
+        A.mul = J.mul; A.ld_mul = J.ld_mul;
+        A.dz = J.Y; A.ld_dz = J.ldy;
+        A.aux = C.aux;
+        A.slope = J.slope; A.ln_eps = J.ln_eps;
+    }
+    for (int j = 0; j < 3; ++j) {
+        const EqdChainJob& C = jobs[at++];
+        if (!plain(C, 1) || C.src_local[0] != 1 || C.out_local >= 0 || !C.lin.Y) return false;
+        // the residual: only the accumulation of dh0acc into itself, and only behind a dh job (the last layer initialises it)
+        if (C.lin.R && !(dh && j == 2 && C.lin.R == C.lin.Y && C.lin.ldr == C.lin.ldy)) return false;
+        A.x[j] = src(C.lin.s[0]);
+        A.xo[j] = out(C.lin);
+        if (j > 0 && (A.x[j].W != A.x[j - 1].W + 64 || A.x[j].wcs != A.x[j - 1].wcs)) return false;
+    }
+    return true;
+}
+static std::atomic<long long> g_chain_resident_bwd_launches{0};
+extern "C" long long eqd_chain_resident_bwd_launches(void) { return g_chain_resident_bwd_launches.load(); }
+
 int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_t st, int* partial_rows) {
     if (njobs <= 0 || njobs > EQD_CHAIN_MAXJOBS) {
         eqd_set_error("eqd_launch_rowchain: %d jobs (1..%d)", njobs, EQD_CHAIN_MAXJOBS);
@@ -1052,6 +1155,13 @@ int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_
         if (!(oc && oc[0]) && cr_fwd_eligible(jobs, njobs, rows)) {
             hipLaunchKernelGGL(k_rowchain_res_fwd, dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
             g_chain_resident_launches.fetch_add(1);
+            return eqd_check_launch("k_rowchain");
+        }
+        ChainResBwdArg barg;
+        if (!(oc && oc[0]) && crb_pack(jobs, njobs, rows, barg)) {
+            if (njobs == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_bwd<true>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, barg);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_bwd<false>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, barg);
+            g_chain_resident_bwd_launches.fetch_add(1);
             return eqd_check_launch("k_rowchain");
         }
     }

@@ -57,7 +57,7 @@ int eqd_tile_edges(void);
 int eqd_is_simulator(void);
 /* The EQD_* environment switches that select kernel forms for tests and A/B measurements (EQD_FUSE_FWD, EQD_FUSE_GATHER,
  * EQD_ATT_SPLIT, EQD_ATT_BWD_SPLIT, EQD_ATT_LB, EQD_ATT_LB_NB, EQD_ATT_DS, EQD_ATT_QDS_NB, EQD_ROWWAVE, EQD_ROW_TILES,
- * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
+ * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_CHAIN_RESIDENT_BWD, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
  * agree on the forms they run.  A caller that changes one of them afterwards calls this to make the library forget its
  * snapshot (nothing in the reference corresponds to it). */
 void eqd_tunables_reload(void);
@@ -65,6 +65,38 @@ void eqd_tunables_reload(void);
  * chain of a 64-wide layer with all weights in LDS, taken where k_rowchain<1, false, 1> runs otherwise; EQD_CHAIN_RESIDENT=0
  * keeps k_rowchain).  Counts launches, also those recorded into a captured graph, not replays. */
 long long eqd_chain_resident_launches(void);
+/* Test aid: the same count for the resident-weights body of the BACKWARD node chain (k_rowchain_res_bwd: the six-job chain of
+ * layers L-2 .. 1 and the five-job chain of the last layer that eqd_model_backward builds with cross_msgs on, under the same
+ * conditions; EQD_CHAIN_RESIDENT=0 turns off both bodies, EQD_CHAIN_RESIDENT_BWD=0 this one alone).  The count above keeps
+ * meaning the forward body. */
+long long eqd_chain_resident_bwd_launches(void);
+/* Test aid: ONE backward node chain of a 64-wide layer with cross messages on the caller's buffers, built by the list builder
+ * eqd_model_backward uses: with_dh = 1 the six-job chain of layers L-2 .. 1 (dh of the layer above from its six sources
+ * dh_X[s] [rows][64] times transposed weights, element (m, k) at dh_W[s][m + k * dh_wcs[s]], plus (1 - skip) dH_above, written
+ * to dH; dh0acc += ...), with_dh = 0 the five-job chain of the last layer (dH_above is the incoming gradient; dh0acc = ...).
+ * Wn2 [64][64]; Wn1 [64][d0 + 192]; y_act, drop_mul (or NULL), dz, d_aggr_msg, d_aggr_cross [rows][64]; dh0acc [rows][d0],
+ * columns 0 .. 63 written; ln_part [*partial_rows][256] (at most ceil(rows / 16) rows).  The model keeps these buffers inside
+ * its scratch arena; here a test can put guard rows behind each. */
+typedef struct EqdNodeChainBwdTest {
+    int32_t rows, with_dh, d0;
+    float skip_weight_h, slope, ln_eps;
+    const float* dh_X[6];
+    const float* dh_W[6];
+    int32_t dh_wcs[6];
+    const float* dH_above;
+    float* dH;
+    const float* Wn2;
+    const float* Wn1;
+    const float* y_act;
+    const float* ln_g;
+    const float* drop_mul;
+    float* dz;
+    float* ln_part;
+    float* d_aggr_msg;
+    float* d_aggr_cross;
+    float* dh0acc;
+} EqdNodeChainBwdTest;
+int eqd_selftest_node_chain_bwd(const EqdNodeChainBwdTest* t, int* partial_rows /* host */, void* stream);
 /* Test aid: one 256-thread workgroup runs the library's cross-lane helpers (DPP moves, v_permlane{16,32}_swap) on in256
  * [256] beside the plain ds_bpermute forms, and the guard-free exponentials of the softmax kernels beside expf / exp2f;
  * mismatch [4] (device ints, zeroed by the caller) receives the number of differing (lane, check) pairs of the exchanges [0],
