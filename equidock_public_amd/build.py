@@ -88,7 +88,7 @@ def build_dock(force=False, verbose=True):
     reduction helpers of csrc/eqd_common.h; its symbols are hidden except the eqd_dock_* entry points."""
     srcs = sorted(glob.glob(os.path.join(HERE, 'csrc_dock', '*.hip')))
     inc = os.path.join(os.path.dirname(HERE), 'include')
-    deps = srcs + [os.path.join(CSRC, 'eqd_common.h'), os.path.join(inc, 'equidock_hip.h'), os.path.join(inc, 'equidock_dock.h')]
+    deps = srcs + sorted(glob.glob(os.path.join(HERE, 'csrc_dock', '*.h'))) + [os.path.join(CSRC, 'eqd_common.h'), os.path.join(inc, 'equidock_hip.h'), os.path.join(inc, 'equidock_dock.h')]
     if force or _stale(DOCK_LIB, deps):
         cmd = [HIPCC] + FLAGS + ['-fvisibility=hidden', '-shared', '-o', DOCK_LIB] + srcs
         if verbose:

@@ -29,6 +29,8 @@ DOCK_ABI_VERSION = 1
 DOCK_GRAPH_ABI = 1
 DOCK_METER_ABI = 1
 METER_COLS = 8             # EQD_DOCK_METER_COLS
+DOCK_QUALITY_ABI = 1
+QUALITY_COLS = 16          # EQD_DOCK_QUALITY_COLS
 
 _dock = None
 _dock_is_sim = False
@@ -67,6 +69,14 @@ def _declare(lib):
     lib.eqd_dock_meter_eval.restype = C.c_int
     lib.eqd_dock_meter_eval.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_quality_abi.restype = C.c_int
+    lib.eqd_dock_quality_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_quality_workspace_bytes.argtypes = [C.c_int] + [C.c_void_p] * 4
+    lib.eqd_dock_quality_init.restype = C.c_int
+    lib.eqd_dock_quality_init.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]
+    lib.eqd_dock_quality_eval.restype = C.c_int
+    lib.eqd_dock_quality_eval.argtypes = ([C.c_int] + [C.c_void_p] * 12 + [C.c_double] * 3 + [C.c_int, C.c_void_p, C.c_void_p,
+                                                                                             C.c_size_t, C.c_void_p])
 
 
 def _bind(path):
@@ -79,6 +89,8 @@ def _bind(path):
         raise _lib.EquidockHipError(f"{path}: dock graph ABI {lib.eqd_dock_graph_abi()} != {DOCK_GRAPH_ABI}")
     if lib.eqd_dock_meter_abi() != DOCK_METER_ABI:
         raise _lib.EquidockHipError(f"{path}: dock meter ABI {lib.eqd_dock_meter_abi()} != {DOCK_METER_ABI}")
+    if lib.eqd_dock_quality_abi() != DOCK_QUALITY_ABI:
+        raise _lib.EquidockHipError(f"{path}: dock quality ABI {lib.eqd_dock_quality_abi()} != {DOCK_QUALITY_ABI}")
     _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
     return lib
 
@@ -324,6 +336,183 @@ class DeviceMeter:
         return f(arr), np.std(arr)
 
 
+# ---- batched docking quality: fnat, LRMSD, iRMSD(bb), DockQ, clashes ------------------------------------------------------
+BACKBONE = ('N', 'CA', 'C', 'O')
+QUALITY_KEYS = ('dockq', 'fnat', 'fnonnat', 'irmsd_backbone', 'lrmsd', 'native_contacts', 'model_contacts', 'shared_contacts',
+                'interface_residues_ligand', 'interface_residues_receptor', 'interface_backbone_rows', 'clashes', 'flags',
+                'pruned_pairs')
+
+
+def quality_pruning_enabled():
+    """EQD_DOCK_QUALITY_PRUNE=0 turns the centroid-and-radius pruning of the residue-pair search off (same results but
+    for the count of pruned pairs)."""
+    return os.environ.get('EQD_DOCK_QUALITY_PRUNE', '1') != '0'
+
+
+def _is_hydrogen(name, element):
+    el = element.strip().upper()
+    if el:
+        return el in ('H', 'D')
+    return name.strip().lstrip('0123456789')[:1].upper() in ('H', 'D')
+
+
+def atom_table(x):
+    """The heavy atoms of a PDB path or of a list of featurize.Residue, in file (list) order:
+    (coordinates [n, 3] float32, index [n] int64 of those rows among ALL ATOM rows - the rows of inference.read_pdb_atoms /
+    featurize.atoms_ragged -, residue offsets [n_res + 1] int32 into the n rows, backbone mask [n] uint8 (atoms named N,
+    CA, C or O), atom names [n]).  A residue is a maximal run of consecutive ATOM rows that share chain, residue number,
+    insertion code and residue name - file order, not the sorted grouping of featurize.read_pdb_residues; a run whose
+    atoms are all hydrogens has no row and no residue."""
+    rows = []              # (residue key, name, element, xyz) of every ATOM row
+    if isinstance(x, (str, os.PathLike)):
+        with open(x) as f:
+            for line in f:
+                if line.startswith('ATOM'):
+                    rows.append(((line[21:22], line[22:26], line[26:27], line[17:20]), line[12:16].strip(),
+                                 line[76:78] if len(line) >= 78 else '',
+                                 (float(line[30:38]), float(line[38:46]), float(line[46:54]))))
+    else:
+        for r in x:
+            key = (r.chain, r.number, '', r.resname)
+            els = r.elements if len(r.elements) == len(r.atom_names) else [''] * len(r.atom_names)
+            for name, el, xyz in zip(r.atom_names, els, r.coords):
+                rows.append((key, name.strip(), el, xyz))
+    index, names, coords, off, prev = [], [], [], [0], None
+    for k, (key, name, el, xyz) in enumerate(rows):
+        new_run = key != prev
+        prev = key
+        if new_run and len(index) > off[-1]:
+            off.append(len(index))
+        if _is_hydrogen(name, el):
+            continue
+        index.append(k)
+        names.append(name)
+        coords.append(xyz)
+    if len(index) > off[-1]:
+        off.append(len(index))
+    names = np.asarray(names, dtype=str)
+    return (np.ascontiguousarray(np.asarray(coords, dtype=np.float32).reshape(-1, 3)), np.asarray(index, dtype=np.int64),
+            np.asarray(off, dtype=np.int32), np.isin(names, BACKBONE).astype(np.uint8), names)
+
+
+def _residue_table(off, n_atoms, what):
+    off = np.asarray(off)
+    if off.ndim != 1 or len(off) < 2 or int(off[0]) != 0 or int(off[-1]) != n_atoms or (np.diff(off.astype(np.int64)) < 1).any():
+        raise ValueError(f"{what}: residue offsets must start at 0, increase strictly and end at the {n_atoms} atom rows")
+    return off.astype(np.int64)
+
+
+class QualityPlan:
+    """Workspace and tables of eqd_dock_quality_eval for one batch of complexes: the per-complex residue offsets (local:
+    [n_res + 1] into the complex's own rows) and backbone masks ([n_atoms], non-zero = N, CA, C or O) go up in ONE copy,
+    the workspace is created and initialised once (init copies the item table and waits for that copy); `eval` then only
+    enqueues launches - it can be captured into a hipGraph."""
+
+    def __init__(self, lig_res_offsets, rec_res_offsets, lig_backbone, rec_backbone, dev):
+        lib = load_dock_library()
+        n = len(lig_res_offsets)
+        if n == 0 or not (n == len(rec_res_offsets) == len(lig_backbone) == len(rec_backbone)):
+            raise ValueError(f"{n} ligand residue tables for {len(rec_res_offsets)} receptor residue tables, "
+                             f"{len(lig_backbone)} ligand and {len(rec_backbone)} receptor backbone masks")
+        lbb = [np.asarray(m).reshape(-1) != 0 for m in lig_backbone]
+        rbb = [np.asarray(m).reshape(-1) != 0 for m in rec_backbone]
+        lro = [_residue_table(o, len(m), f'complex {c}: ligand') for c, (o, m) in enumerate(zip(lig_res_offsets, lbb))]
+        rro = [_residue_table(o, len(m), f'complex {c}: receptor') for c, (o, m) in enumerate(zip(rec_res_offsets, rbb))]
+        self.n, self.dev = n, torch.device(dev)
+        self.lig_atom_off, self.rec_atom_off = _offsets([len(m) for m in lbb]), _offsets([len(m) for m in rbb])
+        self.lig_res_off, self.rec_res_off = _offsets([len(o) - 1 for o in lro]), _offsets([len(o) - 1 for o in rro])
+        self._off = tuple(a.ctypes.data_as(C.c_void_p) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off,
+                                                                  self.rec_res_off))
+        Al, Ar, Rl, Rr = (int(a[-1]) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off, self.rec_res_off))
+        # one staging buffer, one upload: int32 first rows of the ligand | of the receptor residues, uint8 masks
+        host = _staging(4 * (Rl + Rr + 2) + Al + Ar, torch.uint8, self.dev)
+        h = host.numpy()
+        first = h[:4 * (Rl + Rr + 2)].view(np.int32)
+        first[:Rl + 1] = np.concatenate([o[:-1] + int(a) for o, a in zip(lro, self.lig_atom_off)] + [[Al]])
+        first[Rl + 1:] = np.concatenate([o[:-1] + int(a) for o, a in zip(rro, self.rec_atom_off)] + [[Ar]])
+        h[4 * (Rl + Rr + 2):] = np.concatenate(lbb + rbb)
+        self.tables = host.to(self.dev, non_blocking=True)
+        ints = self.tables[:4 * (Rl + Rr + 2)].view(torch.int32)
+        self.lig_first, self.rec_first = ints[:Rl + 1], ints[Rl + 1:]
+        self.lig_bb, self.rec_bb = self.tables[4 * (Rl + Rr + 2):4 * (Rl + Rr + 2) + Al], self.tables[4 * (Rl + Rr + 2) + Al:]
+        self.residue_pairs = int(sum((len(a) - 1) * (len(b) - 1) for a, b in zip(lro, rro)))
+        self.wsb = lib.eqd_dock_quality_workspace_bytes(n, *self._off)
+        if self.wsb == 0:
+            check(2)
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        with _lib.device_guard(self.dev):
+            check(lib.eqd_dock_quality_init(n, *self._off, _lib.ptr(self.ws), C.c_size_t(self.wsb), _stream(self.dev)))
+
+    def eval(self, lig_pred, rec_pred, lig_true, rec_true, out, contact_cutoff=5.0, interface_cutoff=10.0, clash_cutoff=3.0,
+             prune=None):
+        """Enqueue the quality pass on the current stream: [sum n][3] fp32 contiguous inputs (rec_pred may be None: it is
+        rec_true), out [C][16] fp64.  No synchronisation, no allocation, no copy."""
+        prune = quality_pruning_enabled() if prune is None else bool(prune)
+        with _lib.device_guard(self.dev):
+            check(_dock.eqd_dock_quality_eval(self.n, *self._off, _lib.ptr(lig_pred),
+                                              _lib.ptr(rec_pred) if rec_pred is not None else C.c_void_p(0),
+                                              _lib.ptr(lig_true), _lib.ptr(rec_true), _lib.ptr(self.lig_first),
+                                              _lib.ptr(self.rec_first), _lib.ptr(self.lig_bb), _lib.ptr(self.rec_bb),
+                                              C.c_double(float(contact_cutoff)), C.c_double(float(interface_cutoff)),
+                                              C.c_double(float(clash_cutoff)), int(prune), _lib.ptr(out), _lib.ptr(self.ws),
+                                              C.c_size_t(self.wsb), _stream(self.dev)))
+        return out
+
+
+def pose_quality_batch(lig_pred_list, lig_true_list, rec_true_list, lig_res_offsets=None, rec_res_offsets=None,
+                       lig_backbone=None, rec_backbone=None, rec_pred_list=None, contact_cutoff=5.0, interface_cutoff=10.0,
+                       clash_cutoff=3.0, plan=None):
+    """fnat, LRMSD, backbone iRMSD, DockQ (Basu & Wallner 2016) and the steric clashes of C docked complexes in one device
+    pass over every heavy atom (eqd_dock_quality_*; the definitions are in include/equidock_dock.h).  The lists hold device
+    tensors [n_c, 3] of heavy atoms, the model's rows corresponding one to one to the native's; `rec_pred_list` None: the
+    model's receptor is the native's.  Per complex (host arrays, as `atom_table` returns them): the residue offsets
+    [n_res + 1] into its own rows and the backbone mask [n_c] of each side - or a `plan` (QualityPlan) that already holds
+    them, so that repeated evaluation of the same complexes reuses tables and workspace.  fp64 on the device from the
+    fp32 rows; a complex's row is bit-identical alone, in any batch and from run to run.
+
+    Returns a dict of device float64 tensors [C] (QUALITY_KEYS: dockq, fnat, fnonnat, irmsd_backbone, lrmsd,
+    native_contacts, model_contacts, shared_contacts, interface_residues_ligand / _receptor, interface_backbone_rows,
+    clashes, flags - bit 0 / bit 1: the Kabsch of the interface / receptor backbone set took the reflection branch -,
+    pruned_pairs), `quality`, the raw [C][16] buffer, and `plan`.  One upload of the small tables (when no plan is
+    given), one launch sequence; apart from the item-table copy of the workspace's init the call does not synchronise and
+    downloads nothing."""
+    ligs_p, ligs_t, recs_t = list(lig_pred_list), list(lig_true_list), list(rec_true_list)
+    recs_p = None if rec_pred_list is None else list(rec_pred_list)
+    n = len(ligs_p)
+    if not (n == len(ligs_t) == len(recs_t)) or (recs_p is not None and len(recs_p) != n):
+        raise ValueError(f"{n} predicted ligands for {len(ligs_t)} true ligands, {len(recs_t)} true receptors and "
+                         f"{'no' if recs_p is None else len(recs_p)} predicted receptors")
+    if n == 0:
+        raise ValueError("pose_quality_batch: no complexes")
+    ligs_p, ligs_t, recs_t = _meter_rows(ligs_p, 'predicted ligand'), _meter_rows(ligs_t, 'true ligand'), _meter_rows(recs_t, 'true receptor')
+    if recs_p is not None:
+        recs_p = _meter_rows(recs_p, 'predicted receptor')
+    for c in range(n):
+        if ligs_p[c].shape[0] != ligs_t[c].shape[0]:
+            raise ValueError(f"complex {c}: {ligs_p[c].shape[0]} predicted ligand rows for {ligs_t[c].shape[0]} true ones")
+        if recs_p is not None and recs_p[c].shape[0] != recs_t[c].shape[0]:
+            raise ValueError(f"complex {c}: {recs_p[c].shape[0]} predicted receptor rows for {recs_t[c].shape[0]} true ones")
+    dev = ligs_p[0].device
+    if plan is None:
+        if lig_res_offsets is None or rec_res_offsets is None or lig_backbone is None or rec_backbone is None:
+            raise ValueError("pose_quality_batch: residue offsets and backbone masks of both sides (or a plan) are needed")
+        plan = QualityPlan(list(lig_res_offsets), list(rec_res_offsets), list(lig_backbone), list(rec_backbone), dev)
+    if plan.n != n:
+        raise ValueError(f"the plan holds {plan.n} complexes, the lists {n}")
+    for c in range(n):
+        nl, nr = int(plan.lig_atom_off[c + 1] - plan.lig_atom_off[c]), int(plan.rec_atom_off[c + 1] - plan.rec_atom_off[c])
+        if ligs_t[c].shape[0] != nl or recs_t[c].shape[0] != nr:
+            raise ValueError(f"complex {c}: {ligs_t[c].shape[0]} ligand and {recs_t[c].shape[0]} receptor rows for tables of "
+                             f"{nl} and {nr} atoms")
+    out = torch.empty(n, QUALITY_COLS, dtype=torch.float64, device=dev)
+    plan.eval(torch.cat(ligs_p, 0), None if recs_p is None else torch.cat(recs_p, 0), torch.cat(ligs_t, 0),
+              torch.cat(recs_t, 0), out, contact_cutoff=contact_cutoff, interface_cutoff=interface_cutoff,
+              clash_cutoff=clash_cutoff)
+    res = {k: out[:, i] for i, k in enumerate(QUALITY_KEYS)}
+    res.update(quality=out, plan=plan)
+    return res
+
+
 # ---- batched graph construction -------------------------------------------------------------------------------------
 GRAPH_KEYS = ('x', 'res_feat', 'mu_r_norm', 'src', 'dst', 'he')
 last_graph_stats = {}      # of the latest protein_graphs_batch call: proteins, residues, edges, pairs, pruned_pairs, pruning
@@ -517,6 +706,37 @@ def _chunk_metrics(chunk, truths, first, final_lig, rec_atoms, cutoff, dev):
     return rmsd_metrics_batch(lig_pred, lig_true, rec_true, cutoff=cutoff, interface=True)['metrics'].cpu().numpy()
 
 
+def _chunk_quality(chunk, truths, first, final_lig, rec_atoms, cuts, dev):
+    """The quality stage of dock_complexes for one chunk: the heavy-atom rows of the final ligands and of the receptors
+    taken on the device by an index built on the host, one pose_quality_batch (the model's receptor is the receptor given),
+    ONE download of the [C][16] rows - a download of its own, after the meter's."""
+    lig_t, rec_t, gts = [], [], []
+    for k, ((lig_in, rec_in), gt) in enumerate(zip(chunk, truths)):
+        lig_t.append(atom_table(lig_in))
+        rec_t.append(atom_table(rec_in))
+        gts.append(atom_table(gt))
+        if len(lig_t[-1][4]) == 0 or len(rec_t[-1][4]) == 0:
+            raise ValueError(f"complex {first + k}: a side without a heavy atom")
+        if len(lig_t[-1][4]) != len(gts[-1][4]) or (lig_t[-1][4] != gts[-1][4]).any():
+            raise ValueError(f"complex {first + k}: the ligand's heavy-atom names differ from its ground truth's "
+                             f"({len(lig_t[-1][4])} and {len(gts[-1][4])} heavy atoms)")
+    n = len(chunk)
+    idx = [t[1] for t in lig_t + rec_t]
+    n_idx, n_gt = sum(len(a) for a in idx), sum(len(t[0]) for t in gts)
+    hidx, hgt = _staging(n_idx, torch.int64, dev), _staging(3 * n_gt, torch.float32, dev)
+    hidx.numpy()[:] = np.concatenate(idx)
+    hgt.numpy()[:] = np.concatenate([t[0] for t in gts], 0).reshape(-1)
+    didx, dgt = hidx.to(dev, non_blocking=True), hgt.to(dev, non_blocking=True).view(-1, 3)
+    ioff = np.concatenate([[0], np.cumsum([len(a) for a in idx])])
+    goff = np.concatenate([[0], np.cumsum([len(t[0]) for t in gts])])
+    lig_pred = [final_lig[k].index_select(0, didx[ioff[k]:ioff[k + 1]]) for k in range(n)]
+    rec_true = [rec_atoms[k].index_select(0, didx[ioff[n + k]:ioff[n + k + 1]]) for k in range(n)]
+    lig_true = [dgt[goff[k]:goff[k + 1]] for k in range(n)]
+    q = pose_quality_batch(lig_pred, lig_true, rec_true, [t[2] for t in lig_t], [t[2] for t in rec_t], [t[3] for t in lig_t],
+                           [t[3] for t in rec_t], contact_cutoff=cuts[0], interface_cutoff=cuts[1], clash_cutoff=cuts[2])
+    return q['quality'].cpu().numpy()
+
+
 def _sync(dev):
     if dev.type == 'cuda':
         torch.cuda.synchronize(dev)
@@ -545,7 +765,8 @@ def _chunk_graphs(chunk, cutoff, max_neighbor, dev):
 
 def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=None, device=None, cutoff=30.0,
                    max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50,
-                   batched_graphs=True, ground_truth=None, interface_cutoff=8.0):
+                   batched_graphs=True, ground_truth=None, interface_cutoff=8.0, quality=False,
+                   quality_cutoffs=(5.0, 10.0, 3.0)):
     """Dock a list of (ligand, receptor) complexes, each side a PDB path or a list of featurize.Residue (the ligand's
     file / residues in their input pose, the receptor's in the bound pose - the reference's `*_l_b.pdb` and
     `*_r_b_COMPLEX.pdb`).  Per chunk of `max_complexes_per_batch` complexes (all at once by default): graphs on the
@@ -562,8 +783,17 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
     receptor's ground truth is the receptor given).  Each chunk then ends with one rmsd_metrics_batch on the C-alpha rows
     of its final ligands (taken on the device) and one download, and the results gain `crmsd`, `irmsd`, `ligand_rmsd`
     (floats; irmsd NaN without a C-alpha pair closer than `interface_cutoff`) and `interface_pairs`; batch_seconds gains
-    'metrics'.  A ligand whose C-alpha count differs from its ground truth's raises ValueError.  Without it nothing changes."""
+    'metrics'.  A ligand whose C-alpha count differs from its ground truth's raises ValueError.  Without it nothing changes.
+
+    `quality` (needs `ground_truth`): each chunk also ends with one pose_quality_batch over EVERY heavy atom of its final
+    ligands (taken on the device; the model's receptor is the receptor given) and one more download, and the results gain
+    `dockq`, `fnat`, `fnonnat`, `irmsd_backbone`, `lrmsd` (floats, NaN where undefined), `native_contacts`,
+    `model_contacts` and `clashes` (ints); batch_seconds gains 'quality'.  `quality_cutoffs`: contact, interface and clash
+    cutoff.  A ligand whose heavy-atom names differ from its ground truth's raises ValueError naming the complex.
+    quality=False changes nothing."""
     complexes = list(complexes)
+    if quality and ground_truth is None:
+        raise ValueError("quality=True needs ground_truth")
     if ground_truth is not None:
         ground_truth = list(ground_truth)
         if len(ground_truth) != len(complexes):
@@ -611,12 +841,16 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
             t4 = time.perf_counter()
             times = {'graphs': t1 - t0, 'model': t2 - t1, 'rigid': t3 - t2, 'clashes': t4 - t3, 'total': t4 - t0,
                      'n_complexes': len(chunk)}
-            rows = None
+            rows = qrows = None
             if ground_truth is not None:
                 final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
                 rows = _chunk_metrics(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, interface_cutoff, dev)
                 t5 = time.perf_counter()           # (the download has synchronised)
                 times.update(metrics=t5 - t4, total=t5 - t0)
+                if quality:
+                    qrows = _chunk_quality(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, quality_cutoffs, dev)
+                    t6 = time.perf_counter()       # (the download has synchronised)
+                    times.update(quality=t6 - t5, total=t6 - t0)
             for i in range(len(chunk)):
                 results.append({'rotation': rots[i].detach().cpu().numpy(), 'translation': trs[i].detach().cpu().numpy().reshape(3),
                                 'ligand_atoms_docked': docked[i],
@@ -628,6 +862,11 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                 if rows is not None:
                     results[-1].update(crmsd=float(rows[i, 2]), irmsd=float(rows[i, 3]), ligand_rmsd=float(rows[i, 0]),
                                        interface_pairs=int(rows[i, 4]))
+                if qrows is not None:
+                    q = qrows[i]
+                    results[-1].update(dockq=float(q[0]), fnat=float(q[1]), fnonnat=float(q[2]), irmsd_backbone=float(q[3]),
+                                       lrmsd=float(q[4]), native_contacts=int(q[5]), model_contacts=int(q[6]),
+                                       clashes=int(q[11]))
     finally:
         net.train(was_training)
     return results
@@ -657,6 +896,9 @@ def main(argv=None):
     p.add_argument('--device-metrics', action='store_true',
                    help='CRMSD / IRMSD of every complex from one batched device pass per batch on the docked C-alpha atoms '
                         '(needs every <name>_l_b_COMPLEX.pdb) instead of re-reading the written files on the host')
+    p.add_argument('--dockq', action='store_true',
+                   help='fnat, LRMSD, backbone iRMSD, DockQ and the clashes of every docked pose from one batched device pass '
+                        'per batch over every heavy atom (needs every <name>_l_b_COMPLEX.pdb)')
     a = p.parse_args(argv)
     try:
         names = sorted(os.path.basename(f)[:-len('_l_b.pdb')] for f in glob.glob(os.path.join(a.input_dir, '*_l_b.pdb')))
@@ -669,11 +911,12 @@ def main(argv=None):
                 raise FileNotFoundError(f"{rec} is missing (receptor of {nm})")
             complexes.append((os.path.join(a.input_dir, nm + '_l_b.pdb'), rec))
         truths = None
-        if a.device_metrics:
+        if a.device_metrics or a.dockq:
             truths = [os.path.join(a.gt_dir, nm + '_l_b_COMPLEX.pdb') for nm in names]
             for gt in truths:
                 if not os.path.isfile(gt):
-                    raise FileNotFoundError(f"{gt} is missing (--device-metrics needs the ground-truth ligand of every complex)")
+                    raise FileNotFoundError(f"{gt} is missing ({'--device-metrics' if a.device_metrics else '--dockq'} "
+                                            "needs the ground-truth ligand of every complex)")
         os.makedirs(a.out_dir, exist_ok=True)
         dev = torch.device(a.device)
         net = load_checkpoint(a.checkpoint, dev)
@@ -682,9 +925,9 @@ def main(argv=None):
         res = dock_complexes(net, complexes, remove_clashes=a.remove_clashes, max_complexes_per_batch=a.batch or None,
                              device=dev, cutoff=float(ca.get('graph_cutoff', 30.0)),
                              max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it,
-                             batched_graphs=not a.no_batched_graphs, ground_truth=truths)
+                             batched_graphs=not a.no_batched_graphs, ground_truth=truths, quality=a.dockq)
         suffix = '_EQUIDOCK_NO_CLASHES.pdb' if a.remove_clashes else '_EQUIDOCK.pdb'
-        crmsd, irmsd = [], []
+        crmsd, irmsd, dockq = [], [], []
         for nm, (lig_path, rec_path), r in zip(names, complexes, res):
             out = os.path.join(a.out_dir, nm + '_l_b' + suffix)
             INF.write_pdb_coordinates(lig_path, r['ligand_atoms'], out)
@@ -703,12 +946,23 @@ def main(argv=None):
                 crmsd.append(c)
                 irmsd.append(i)
                 line += f"  CRMSD {c:.3f}  IRMSD {i:.3f}"
+            if a.dockq:
+                dockq.append(r['dockq'])
+                line += (f"  DockQ {r['dockq']:.3f}  fnat {r['fnat']:.3f}  LRMSD {r['lrmsd']:.3f}  "
+                         f"iRMSD(bb) {r['irmsd_backbone']:.3f}  clashes {r['clashes']}")
             print(line, flush=True)
         wall = time.perf_counter() - t0
         print(f"Mean runtime: {wall / len(res):.4f} s per complex ({len(res)} complexes, {wall:.3f} s)")
         if crmsd:
             print("CRMSD median/mean/std: %.3f / %.3f / %.3f" % _stats(crmsd))
             print("IRMSD median/mean/std: %.3f / %.3f / %.3f" % _stats(irmsd))
+        if a.dockq:
+            dq = np.asarray(dockq, dtype=np.float64)
+            ok = dq[~np.isnan(dq)]                  # (DockQ is undefined for a native without a contact)
+            print("DockQ median/mean/std: %.3f / %.3f / %.3f" % (_stats(ok) if ok.size else (float('nan'),) * 3))
+            print("CAPRI classes (DockQ): incorrect %d  acceptable %d  medium %d  high %d" %
+                  (int((ok < 0.23).sum()), int(((ok >= 0.23) & (ok < 0.49)).sum()), int(((ok >= 0.49) & (ok < 0.80)).sum()),
+                   int((ok >= 0.80).sum())) + ("  undefined %d" % (dq.size - ok.size) if ok.size < dq.size else ""))
     except Exception as e:          # noqa: BLE001 - a command-line tool: report and exit non-zero
         print(f"error: {type(e).__name__}: {e}", file=sys.stderr)
         return 1

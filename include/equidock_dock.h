@@ -143,6 +143,64 @@ EQD_DOCK_API int eqd_dock_meter_eval(int n_complex, const int32_t* lig_off, cons
                                      const float* rec_true, double cutoff, int interface, double* metrics,
                                      void* workspace, size_t ws_bytes, void* stream);
 
+/*
+ * Batched docking quality: fnat, ligand RMSD after superposing the receptors, backbone RMSD of the interface residues
+ * and their summary DockQ (Basu & Wallner 2016), plus the steric clashes of the model, for C complexes in one device pass
+ * over EVERY heavy atom.  fp64 arithmetic from the fp32 inputs; a complex's row of results is bit-identical alone, in any
+ * batch, at any position and from run to run.
+ *
+ * Layout: the complexes are stored one after another; the model's rows correspond one to one to the native's.
+ *   lig_pred, lig_true [A_l][3] fp32, rec_pred, rec_true [A_r][3] fp32 (rec_pred may be NULL: it is rec_true)
+ *   lig_atom_off / rec_atom_off [C + 1]  HOST int32, starting at 0: the atom rows of complex c, >= 1 on each side
+ *   lig_res_off / rec_res_off [C + 1]    HOST int32, starting at 0: its residues, 1 <= residues <= atoms on each side
+ *   lig_res_first [R_l + 1], rec_res_first [R_r + 1]  int32: the first atom row (global) of every residue; a complex's
+ *     residues tile its atom rows in order (the kernels hold every range inside the complex's rows whatever the table
+ *     says; the host cannot read it, the caller has to get it right)
+ *   lig_backbone [A_l], rec_backbone [A_r]  uint8: non-zero for the atoms named N, CA, C or O
+ * Definitions: d = sqrt((dx dx + dy dy) + dz dz) < cutoff.  A contact is a (ligand residue, receptor residue) pair with
+ * an atom pair under contact_cutoff; N / M / S count the contacts of the native, of the model, of both.  An interface
+ * residue has a NATIVE atom pair under interface_cutoff to the other side.
+ *   quality [C][EQD_DOCK_QUALITY_COLS] fp64:
+ *     0 DockQ = (fnat + 1 / (1 + (iRMSD / 1.5)^2) + 1 / (1 + (LRMSD / 8.5)^2)) / 3, NaN when a term is
+ *     1 fnat = S / N (NaN when N = 0), 2 fnonnat = (M - S) / M (0 when M = 0),
+ *     3 iRMSD(bb): Kabsch RMSD of the model onto the native over the backbone rows of the interface residues of both
+ *       sides (NaN without such a row),
+ *     4 LRMSD(bb): the Kabsch transform of rec_pred onto rec_true over the receptor's backbone rows applied to lig_pred,
+ *       RMSD to lig_true over the ligand's backbone rows (NaN without a backbone row on either side),
+ *     5 N, 6 M, 7 S, 8 / 9 interface residues of the ligand / receptor, 10 interface backbone rows,
+ *     11 atom pairs of the model under clash_cutoff, 12 flags (bit 0: the interface set took the reflection branch
+ *     det(V U^T) < 0, bit 1: the receptor set did), 13 (residue pair, pose) tests the bound pruned (each residue pair is
+ *     tested once in the native and once in the model; 0 with prune == 0), 14 and 15: 0
+ * prune != 0: a residue pair of a pose is not evaluated when (distance of the atom centroids - radius - radius) >=
+ * max(cutoffs) + 1e-6 - no atom pair of it can be under a cutoff - which changes no other column.
+ * Sequence: workspace_bytes -> init (once per set of offsets) -> eval (any number of times).
+ */
+#define EQD_DOCK_QUALITY_ABI 1
+#define EQD_DOCK_QUALITY_COLS 16
+EQD_DOCK_API int eqd_dock_quality_abi(void);
+
+/* Workspace of a batch with these host offsets; 0 when they are invalid or do not fit 32-bit offsets
+ * (eqd_dock_last_error says why). */
+EQD_DOCK_API size_t eqd_dock_quality_workspace_bytes(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                                     const int32_t* lig_res_off, const int32_t* rec_res_off);
+
+/* Validates the offsets and writes the batch's work-item table into the workspace (a host-to-device copy; this call
+ * waits for that copy). */
+EQD_DOCK_API int eqd_dock_quality_init(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                       const int32_t* lig_res_off, const int32_t* rec_res_off, void* workspace,
+                                       size_t ws_bytes, void* stream);
+
+/* Enqueues the quality pass (six launches, whatever C is) on a workspace prepared by eqd_dock_quality_init with the
+ * same offsets.  No synchronisation, no allocation, no host-device copy: the call can be captured into a hipGraph.
+ * Every cutoff must be finite and > 0. */
+EQD_DOCK_API int eqd_dock_quality_eval(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                       const int32_t* lig_res_off, const int32_t* rec_res_off, const float* lig_pred,
+                                       const float* rec_pred, const float* lig_true, const float* rec_true,
+                                       const int32_t* lig_res_first, const int32_t* rec_res_first,
+                                       const uint8_t* lig_backbone, const uint8_t* rec_backbone, double contact_cutoff,
+                                       double interface_cutoff, double clash_cutoff, int prune, double* quality,
+                                       void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
