@@ -203,6 +203,98 @@ EqdAtbJob atb_job(const float* X, int ldx, int M, const float* Y, int ldy, int N
     return J;
 }
 
+// The node projections of one layer - P, Q (the split first edge Linear), attention q / k / v - from h in global memory or
+// from the LDS tile `loc` of a row chain.  Returns the number of jobs written to cj (2 or 5).
+struct NodePre {
+    int N, d, da, ldw1;
+    float slope, eps;
+    bool cross;
+    const float *W1, *B1, *WQ, *WK, *WV;
+    float *P, *Q, *qa, *ka, *va;
+    uint16_t *qa_b, *ka_b, *va_b;      // bf16 storage mode: q / k / v leave the projections as bf16 only (Y = NULL), or NULL
+};
+int node_pre_jobs(const NodePre& n, const float* hsrc, int loc, EqdChainJob* cj) {
+    int nj = 0;
+    auto add = [&](float* Y, int M, int ldy, const float* Wp, int w_rs, const float* bias, int act) {
+        EqdChainJob& C = cj[nj++];
+        memset(&C, 0, sizeof(C));
+        C.lin = lin_job(n.N, M, Y, ldy, n.slope, n.eps);
+        lin_src(C.lin, 0, hsrc, n.d, n.d, Wp, w_rs, 1);
+        C.lin.nsrc = 1; C.lin.bias = bias; C.lin.act = act;
+        for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
+        C.src_local[0] = loc;
+        C.out_local = -1;
+    };
+    add(n.P, 64, 64, n.W1, n.ldw1, nullptr, 0);
+    add(n.Q, 64, 64, n.W1 + n.d, n.ldw1, n.B1, 0);
+    if (n.cross) {
+        add(n.qa, n.d, n.da, n.WQ, n.d, nullptr, 1);
+        add(n.ka, n.d, n.da, n.WK, n.d, nullptr, 1);
+        add(n.va, n.d, n.da, n.WV, n.d, nullptr, 0);
+        if (n.qa_b) {
+            cj[nj - 3].lin.Yb = n.qa_b; cj[nj - 2].lin.Yb = n.ka_b; cj[nj - 1].lin.Yb = n.va_b;
+            for (int i = nj - 3; i < nj; ++i) cj[i].lin.ldyb = 64;
+        }
+        if (n.da != n.d)
+            for (int i = nj - 3; i < nj; ++i) cj[i].lin.pad_to = n.da;
+    }
+    return nj;
+}
+// The forward row chain of one layer's node update, as eqd_model_forward launches it: node_mlp([h, aggr_msg, aggr_cross, h0])
+// -> LeakyReLU [-> dropout] -> LayerNorm (a1n, LDS tile 0) -> node_mlp.4 (+ skip) = h_out [-> LDS tile 1 -> the carried jobs:
+// the next layer's projections (`next`) or the head's mlp_h_mean_ROT (`head`)].  Returns the number of jobs (2, 3, 4 or 7).
+// (Also built by eqd_selftest_node_chain_fwd: the same lists on test buffers.)
+struct NodeFwdChain {
+    int N, d, da, d0, dh, ldn, ld_a1n;
+    float slope, eps, skip;
+    const float *h, *aggr_msg, *aggr_cross, *h0, *Wn1, *Bn1, *ln_g, *ln_b, *Wn2, *Bn2, *drop_mul;
+    float *a1n, *y_act, *h_out;
+    uint16_t *a1n_b, *hb_out;      // bf16 storage mode: the saved copies (or NULL)
+    const NodePre* next;           // carried: the next layer's projections, or NULL
+    const EqdLinJob* head;         // carried: the head's job on h_out, or NULL
+};
+int node_fwd_chain(const NodeFwdChain& c, EqdChainJob* cj) {
+    const int d = c.d;
+    EqdLinJob j1 = lin_job(c.N, d, c.a1n, d, c.slope, c.eps);
+    lin_src(j1, 0, c.h, d, d, c.Wn1, c.ldn, 1);
+    lin_src(j1, 1, c.aggr_msg, 64, 64, c.Wn1 + d, c.ldn, 1);
+    lin_src(j1, 2, c.aggr_cross, c.da, d, c.Wn1 + d + 64, c.ldn, 1);
+    lin_src(j1, 3, c.h0, c.d0, c.d0, c.Wn1 + 2 * d + 64, c.ldn, 1);
+    j1.nsrc = 4; j1.bias = c.Bn1; j1.act = 1; j1.ln_g = c.ln_g; j1.ln_b = c.ln_b;
+    j1.pre_ln = c.y_act; j1.ld_pre = d;
+    j1.Yb = c.a1n_b; j1.ldyb = c.ld_a1n;               // bf16 storage mode: a1n is saved as bf16 (Y = NULL)
+    j1.mul = c.drop_mul; j1.ld_mul = d;                // node_mlp.1 (Dropout) in training mode
+    EqdLinJob j2 = lin_job(c.N, c.dh, c.h_out, c.dh, c.slope, c.eps);
+    lin_src(j2, 0, c.a1n, d, d, c.Wn2, d, 1);
+    j2.nsrc = 1; j2.bias = c.Bn2;
+    j2.Yb = c.hb_out; j2.ldyb = c.dh;                  // bf16 storage mode: the saved copy of h[l + 1] (or NULL)
+    if (d == c.dh) {
+        j2.alpha = c.skip; j2.beta = 1.f - c.skip; j2.R = c.h; j2.ldr = d;
+    }
+    // one launch: the LayerNorm output stays in LDS for node_mlp.4
+    memset(cj, 0, 2 * sizeof(EqdChainJob));
+    for (int k = 0; k < 2; ++k) {
+        for (int i = 0; i < EQD_MAX_SRC; ++i) cj[k].src_local[i] = -1;
+        cj[k].out_local = -1;
+    }
+    cj[0].lin = j1; cj[0].out_local = 0;
+    cj[1].lin = j2; cj[1].src_local[0] = 0;
+    int nj = 2;
+    if (c.next) {
+        cj[1].out_local = 1;
+        nj += node_pre_jobs(*c.next, c.h_out, 1, cj + 2);
+    } else if (c.head) {
+        cj[1].out_local = 1;
+        EqdChainJob& C = cj[nj++];
+        memset(&C, 0, sizeof(C));
+        C.lin = *c.head;
+        for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
+        C.src_local[0] = 1;
+        C.out_local = -1;
+    }
+    return nj;
+}
+
 // The backward row chain of one layer, as eqd_model_backward launches it: [dh of the layer above (kept as LDS tile 2) ->]
 // da1n = alpha dH Wn2 (tile 0) -> LeakyReLU / LayerNorm backward (dz, tile 1, the ln_part rows) -> dz times the column
 // blocks of Wn1: d aggr_msg, d aggr_cross (cross messages only), the embedding columns of d h0 accumulated over the layers.
@@ -593,6 +685,40 @@ extern "C" int eqd_model_layer_state(const EqdModelDesc* m, const EqdGraph* g, c
     return EQD_OK;
 }
 
+// Test / debug aid: the node-level tensors of layer `layer` inside the `saved` buffer of an fp32 forward - what the node
+// projections and the node update wrote: out[0 .. 6] = P, Q [N][64], q, k, v [N][*d_att], a1n [N][d_in], and hm [N][64] (the
+// head's mlp_h_mean_ROT output; the same pointer for every layer).
+extern "C" int eqd_model_node_state(const EqdModelDesc* m, const EqdGraph* g, const void* saved, size_t saved_bytes, int layer,
+                                    const float** out, int* d_in, int* d_att) {
+    if (int rc = eqd_model_check(m, g)) return rc;
+    if (!saved || !out || !d_in || !d_att) {
+        eqd_set_error("eqd_model_node_state: NULL argument");
+        return EQD_ERR_NULL;
+    }
+    const Dims D = make_dims(m, g);
+    if (layer < 0 || layer >= D.L) {
+        eqd_set_error("eqd_model_node_state: layer %d outside 0..%d", layer, D.L - 1);
+        return EQD_ERR_SHAPE;
+    }
+    if (m->storage_bf16) {
+        eqd_set_error("eqd_model_node_state: fp32 storage only");
+        return EQD_ERR_UNSUPPORTED;
+    }
+    EqdArena A(const_cast<void*>(saved), saved_bytes);
+    Saved S;
+    carve_saved(D, g, A, S, false, false, edge_state_saved(m, g));
+    if (!A.ok) {
+        eqd_set_error("eqd_model_node_state: saved buffer too small");
+        return EQD_ERR_WORKSPACE;
+    }
+    const LayerSaved& Ls = S.lay[layer];
+    out[0] = Ls.P; out[1] = Ls.Q; out[5] = Ls.a1n; out[6] = S.hm;
+    out[2] = m->cross_msgs ? Ls.qa : nullptr; out[3] = m->cross_msgs ? Ls.ka : nullptr; out[4] = m->cross_msgs ? Ls.va : nullptr;
+    *d_in = D.d_in(layer);
+    *d_att = D.d_att(layer);
+    return EQD_OK;
+}
+
 // Test / debug aid: the LeakyReLU branch decisions of a forward whose state is in `saved`, as one byte per element
 // (1 = pre-activation > 0).  The backward takes its node-level masks from the saved activations (y_act, qa, ka, hm: the
 // sign of LeakyReLU(z) is the sign of z) and the edge-level ones from the per-tile recompute; both are reproduced here
@@ -752,39 +878,24 @@ extern "C" int eqd_model_forward(const EqdModelDesc* m, const EqdGraph* g, const
     const float* const* gp = params + (size_t)EQD_PARAMS_PER_LAYER * D.L;
 
     RC(eqd_launch_embed_fwd(g, gp[G_EMB], m->d_emb, m->use_mean_node_features, S.h[0], D.d0, st));
-    // node projections of layer `l` from h (global) or from the LDS tile `loc` of a row chain:
-    // P, Q (split first edge Linear), attention q / k / v
-    auto node_pre_jobs = [&](int l, const float* hsrc, int loc, EqdChainJob* cj) -> int {
+    // node projections of layer `l` (node_pre_jobs: from h in global memory, or from the LDS tile of a row chain)
+    auto node_pre = [&](int l) -> NodePre {
         const float* const* p = params + (size_t)EQD_PARAMS_PER_LAYER * l;
-        const int d = D.d_in(l);
         const LayerSaved& Ls = S.lay[l];
-        int nj = 0;
-        auto add = [&](float* Y, int M, int ldy, const float* Wp, int w_rs, const float* bias, int act) {
-            EqdChainJob& C = cj[nj++];
-            memset(&C, 0, sizeof(C));
-            C.lin = lin_job(N, M, Y, ldy, slope, eps);
-            lin_src(C.lin, 0, hsrc, d, d, Wp, w_rs, 1);
-            C.lin.nsrc = 1; C.lin.bias = bias; C.lin.act = act;
-            for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
-            C.src_local[0] = loc;
-            C.out_local = -1;
-        };
-        add(Ls.P, 64, 64, p[P_W1], D.ldw1(l), nullptr, 0);
-        add(Ls.Q, 64, 64, p[P_W1] + d, D.ldw1(l), p[P_B1], 0);
-        if (m->cross_msgs) {
-            const int da = D.d_att(l);
-            add(Ls.qa, d, da, p[P_WQ], d, nullptr, 1);
-            add(Ls.ka, d, da, p[P_WK], d, nullptr, 1);
-            add(Ls.va, d, da, p[P_WV], d, nullptr, 0);
-            if (Ls.qa_b) {      // bf16 storage mode: q / k / v leave the projections as bf16 only (Y = NULL)
-                cj[nj - 3].lin.Yb = Ls.qa_b; cj[nj - 2].lin.Yb = Ls.ka_b; cj[nj - 1].lin.Yb = Ls.va_b;
-                for (int i = nj - 3; i < nj; ++i) cj[i].lin.ldyb = 64;
-            }
-            if (da != d)
-                for (int i = nj - 3; i < nj; ++i) cj[i].lin.pad_to = da;
-        }
-        return nj;
+        NodePre n;
+        n.N = N; n.d = D.d_in(l); n.da = D.d_att(l); n.ldw1 = D.ldw1(l);
+        n.slope = slope; n.eps = eps; n.cross = m->cross_msgs != 0;
+        n.W1 = p[P_W1]; n.B1 = p[P_B1]; n.WQ = p[P_WQ]; n.WK = p[P_WK]; n.WV = p[P_WV];
+        n.P = Ls.P; n.Q = Ls.Q; n.qa = Ls.qa; n.ka = Ls.ka; n.va = Ls.va;
+        n.qa_b = Ls.qa_b; n.ka_b = Ls.ka_b; n.va_b = Ls.va_b;
+        return n;
     };
+    // the head's mlp_h_mean_ROT on h[L]
+    EqdLinJob jm = lin_job(N, 64, S.hm, 64, slope, eps);
+    lin_src(jm, 0, S.h[D.L], D.dh, D.dh, gp[G_WM], D.dh, 1);
+    jm.nsrc = 1; jm.bias = gp[G_BM]; jm.act = 1;
+    if (drop) { jm.mul = drop->head; jm.ld_mul = 64; }      // mlp_h_mean_ROT.1 (Dropout) in training mode
+    bool head_in_chain = false;      // ... was computed by the last layer's node-update chain
     bool proj_in_chain = false;      // layer l's projections were computed by layer l - 1's node-update chain
     for (int l = 0; l < D.L; ++l) {
         const float* const* p = params + (size_t)EQD_PARAMS_PER_LAYER * l;
@@ -798,7 +909,8 @@ extern "C" int eqd_model_forward(const EqdModelDesc* m, const EqdGraph* g, const
         //      layer's node-update chain already carried them (large batches, see below) ---------------------
         if (!proj_in_chain) {
             EqdChainJob cj[8];
-            const int nj = node_pre_jobs(l, h, -1, cj);
+            const NodePre np = node_pre(l);
+            const int nj = node_pre_jobs(np, h, -1, cj);
             EqdLinJob jobs[8];
             for (int i = 0; i < nj; ++i) jobs[i] = cj[i].lin;
             RC(eqd_linear(jobs, nj, st));
@@ -832,59 +944,45 @@ extern "C" int eqd_model_forward(const EqdModelDesc* m, const EqdGraph* g, const
             RC(eqd_edge_message_fwd(g, &ep, Ls.P, Ls.Q, S.x[l], Ls.aggr_msg, S.x[l + 1], st));
             if (sat != st) HIPOK(hipStreamWaitEvent(st, cx->join_a, 0));
         }
-        // ---- node update: node_mlp([h, aggr_msg, aggr_cross, h0]) -> LayerNorm, then node_mlp.4 (+ skip).
-        //      (A fused row chain of these + the next layer's projections measured SLOWER: 46 vs 33 us,
-        //       because the five projections then run one after the other instead of side by side.) -----------
-        const int ldn = D.ldwn(l);
-        EqdLinJob j1 = lin_job(N, d, Ls.a1n, d, slope, eps);
-        lin_src(j1, 0, h, d, d, p[P_WN1], ldn, 1);
-        lin_src(j1, 1, Ls.aggr_msg, 64, 64, p[P_WN1] + d, ldn, 1);
-        lin_src(j1, 2, Ls.aggr_cross, da, d, p[P_WN1] + d + 64, ldn, 1);
-        lin_src(j1, 3, S.h[0], D.d0, D.d0, p[P_WN1] + 2 * d + 64, ldn, 1);
-        j1.nsrc = 4; j1.bias = p[P_BN1]; j1.act = 1; j1.ln_g = p[P_NLG]; j1.ln_b = p[P_NLB];
-        j1.pre_ln = Ls.y_act; j1.ld_pre = d;
-        j1.Yb = Ls.a1n_b; j1.ldyb = Ls.ld_a1n;               // bf16 storage mode: a1n is saved as bf16 (Y = NULL)
-        j1.mul = drop_node(D, drop, l); j1.ld_mul = d;       // node_mlp.1 (Dropout) in training mode
-        EqdLinJob j2 = lin_job(N, D.dh, S.h[l + 1], D.dh, slope, eps);
-        lin_src(j2, 0, Ls.a1n, d, d, p[P_WN2], d, 1);
-        j2.nsrc = 1; j2.bias = p[P_BN2];
-        j2.Yb = S.hb[l + 1]; j2.ldyb = D.dh;                 // bf16 storage mode: the saved copy of h[l + 1] (or NULL)
-        if (d == D.dh) {
-            j2.alpha = m->skip_weight_h; j2.beta = 1.f - m->skip_weight_h; j2.R = h; j2.ldr = d;
+        // ---- node update: node_mlp([h, aggr_msg, aggr_cross, h0]) -> LayerNorm, then node_mlp.4 (+ skip): one launch, the
+        //      LayerNorm output stays in LDS for node_mlp.4 (node_fwd_chain) ---------------------------------------------
+        NodeFwdChain fc;
+        fc.N = N; fc.d = d; fc.da = da; fc.d0 = D.d0; fc.dh = D.dh; fc.ldn = D.ldwn(l); fc.ld_a1n = Ls.ld_a1n;
+        fc.slope = slope; fc.eps = eps; fc.skip = m->skip_weight_h;
+        fc.h = h; fc.aggr_msg = Ls.aggr_msg; fc.aggr_cross = Ls.aggr_cross; fc.h0 = S.h[0];
+        fc.Wn1 = p[P_WN1]; fc.Bn1 = p[P_BN1]; fc.ln_g = p[P_NLG]; fc.ln_b = p[P_NLB]; fc.Wn2 = p[P_WN2]; fc.Bn2 = p[P_BN2];
+        fc.drop_mul = drop_node(D, drop, l);
+        fc.a1n = Ls.a1n; fc.y_act = Ls.y_act; fc.h_out = S.h[l + 1]; fc.a1n_b = Ls.a1n_b; fc.hb_out = S.hb[l + 1];
+        fc.next = nullptr; fc.head = nullptr;
+        // The next layer's projections (behind the last layer: the head's mlp_h_mean_ROT) ride in this chain, reading
+        // h(l+1) from the LDS tile - one launch, and one pass over the h rows, less per layer - where a chain's jobs run one
+        // after the other on weights in LDS anyway:
+        //  - large batches (row chains on k_rowres; round 5: in bf16 mode the 69-wide first layer's chain runs on
+        //    k_rowres80 at these sizes and carries layer 1's projections the same way);
+        //  - small batches, fp32, cross messages, 64-wide layers: the resident body k_rowchain_res_fwd<5> / <1>
+        //    (eqd_chainres_inl.h), decided here, BEFORE the list is built, by what eqd_launch_rowchain will ask of it -
+        //    a list it does not take in the carrying form still runs, on k_rowchain, with the same result.
+        // (On the staged k_rowchain body the carried projections measured slower, 46 vs 33 us: every appended job paid its
+        //  own prologue, staging steps and barriers in series.  Layer 0's 69-wide chain stays on that body at small sizes
+        //  and carries nothing.)
+        const bool carry_small = d == 64 && D.dh == 64 && D.d0 > 64 && D.d0 <= 80 && da == 64 && m->cross_msgs &&
+                                 !m->storage_bf16 && eqd_chain_carries_proj(N);
+        proj_in_chain = l + 1 < D.L && D.d_in(l + 1) == 64 && D.dh == 64 && 2 + (m->cross_msgs ? 5 : 2) <= EQD_CHAIN_MAXJOBS &&
+                        (((d == 64 || (m->storage_bf16 && eqd_rowres80_on())) && eqd_rows_resident(N)) ||
+                         (carry_small && D.d_att(l + 1) == 64));
+        head_in_chain = l + 1 == D.L && carry_small;
+        NodePre np;
+        if (proj_in_chain) {
+            np = node_pre(l + 1);
+            fc.next = &np;
+        } else if (head_in_chain) {
+            fc.head = &jm;
         }
-        {   // one launch: the LayerNorm output stays in LDS for node_mlp.4
-            EqdChainJob cj[EQD_CHAIN_MAXJOBS];
-            memset(cj, 0, sizeof(cj));
-            for (int k = 0; k < 2; ++k) {
-                for (int i = 0; i < EQD_MAX_SRC; ++i) cj[k].src_local[i] = -1;
-                cj[k].out_local = -1;
-            }
-            cj[0].lin = j1; cj[0].out_local = 0;
-            cj[1].lin = j2; cj[1].src_local[0] = 0;
-            int nj = 2;
-            // Large batches (row chains on k_rowres, where a wave runs a chain's jobs one after the other anyway): the
-            // next layer's projections ride in this chain, reading h(l+1) from the LDS tile - one launch, and one
-            // pass over the h rows, less per layer.  (With the four-wave kernels of small batches this was measured
-            // slower: 46 vs 33 us, the five projections then run one after the other instead of side by side; layer 0's
-            // 69-wide chain stays on those kernels at every size, so it never carries projections.)
-            // (round 5: in bf16 mode the 69-wide first layer's chain runs on k_rowres80 at these sizes and carries layer 1's
-            //  projections the same way)
-            proj_in_chain = l + 1 < D.L && (d == 64 || (m->storage_bf16 && eqd_rowres80_on())) && D.d_in(l + 1) == 64 &&
-                            D.dh == 64 && eqd_rows_resident(N) && 2 + (m->cross_msgs ? 5 : 2) <= EQD_CHAIN_MAXJOBS;
-            if (proj_in_chain) {
-                cj[1].out_local = 1;
-                nj += node_pre_jobs(l + 1, S.h[l + 1], 1, cj + 2);
-            }
-            RC(eqd_launch_rowchain(cj, nj, N, st));
-        }
+        EqdChainJob cj[EQD_CHAIN_MAXJOBS];
+        const int nj = node_fwd_chain(fc, cj);
+        RC(eqd_launch_rowchain(cj, nj, N, st));
     }
-    {
-        EqdLinJob jm = lin_job(N, 64, S.hm, 64, slope, eps);
-        lin_src(jm, 0, S.h[D.L], D.dh, D.dh, gp[G_WM], D.dh, 1);
-        jm.nsrc = 1; jm.bias = gp[G_BM]; jm.act = 1;
-        if (drop) { jm.mul = drop->head; jm.ld_mul = 64; }      // mlp_h_mean_ROT.1 (Dropout) in training mode
-        RC(eqd_linear(&jm, 1, st));
-    }
+    if (!head_in_chain) RC(eqd_linear(&jm, 1, st));
     // ---- keypoint head ----------------------------------------------------------------------------------
     const float* H = S.h[D.L];
     const float* Z = S.x[D.L];
@@ -1364,4 +1462,52 @@ extern "C" int eqd_selftest_node_chain_bwd(const EqdNodeChainBwdTest* t, int* pa
     EqdChainJob cj[8];
     const int nj = node_bwd_chain(nc, cj);
     return eqd_launch_rowchain(cj, nj, t->rows, (hipStream_t)stream, partial_rows);
+}
+
+// Test aid: the forward row chain of one 64-wide layer on the caller's buffers, through the list builders eqd_model_forward
+// uses (node_fwd_chain, node_pre_jobs) - so that a test can put guard rows behind a1n, y_act, h_out and the carried jobs'
+// outputs, which the model keeps inside its state arena.
+extern "C" int eqd_selftest_node_chain_fwd(const EqdNodeChainFwdTest* t, void* stream) {
+    if (!t || !t->h || !t->aggr_msg || !t->aggr_cross || !t->h0 || !t->Wn1 || !t->Bn1 || !t->ln_g || !t->ln_b || !t->Wn2 ||
+        !t->Bn2 || !t->a1n || !t->y_act || !t->h_out) {
+        eqd_set_error("eqd_selftest_node_chain_fwd: NULL argument");
+        return EQD_ERR_NULL;
+    }
+    if (t->rows <= 0 || t->d0 < 64 || t->d0 > 80 || (t->form != 0 && t->form != 1 && t->form != 5)) {
+        eqd_set_error("eqd_selftest_node_chain_fwd: rows=%d d0=%d form=%d", t->rows, t->d0, t->form);
+        return EQD_ERR_SHAPE;
+    }
+    if (t->form == 5 ? (!t->W1 || !t->B1 || !t->WQ || !t->WK || !t->WV || !t->P || !t->Q || !t->qa || !t->ka || !t->va)
+                     : (t->form == 1 && (!t->WM || !t->BM || !t->hm))) {
+        eqd_set_error("eqd_selftest_node_chain_fwd: NULL argument of a carried job");
+        return EQD_ERR_NULL;
+    }
+    g_bf16_mode = 0;
+    const int d = 64;
+    NodeFwdChain fc;
+    fc.N = t->rows; fc.d = d; fc.da = d; fc.d0 = t->d0; fc.dh = d; fc.ldn = t->d0 + 2 * d + 64; fc.ld_a1n = d;
+    fc.slope = t->slope; fc.eps = t->ln_eps; fc.skip = t->skip_weight_h;
+    fc.h = t->h; fc.aggr_msg = t->aggr_msg; fc.aggr_cross = t->aggr_cross; fc.h0 = t->h0;
+    fc.Wn1 = t->Wn1; fc.Bn1 = t->Bn1; fc.ln_g = t->ln_g; fc.ln_b = t->ln_b; fc.Wn2 = t->Wn2; fc.Bn2 = t->Bn2;
+    fc.drop_mul = t->drop_mul;
+    fc.a1n = t->a1n; fc.y_act = t->y_act; fc.h_out = t->h_out; fc.a1n_b = nullptr; fc.hb_out = nullptr;
+    fc.next = nullptr; fc.head = nullptr;
+    NodePre np;
+    EqdLinJob jm;
+    if (t->form == 5) {
+        np.N = t->rows; np.d = d; np.da = d; np.ldw1 = 2 * d; np.slope = t->slope; np.eps = t->ln_eps; np.cross = true;
+        np.W1 = t->W1; np.B1 = t->B1; np.WQ = t->WQ; np.WK = t->WK; np.WV = t->WV;
+        np.P = t->P; np.Q = t->Q; np.qa = t->qa; np.ka = t->ka; np.va = t->va;
+        np.qa_b = np.ka_b = np.va_b = nullptr;
+        fc.next = &np;
+    } else if (t->form == 1) {
+        jm = lin_job(t->rows, 64, t->hm, 64, t->slope, t->ln_eps);
+        lin_src(jm, 0, t->h_out, d, d, t->WM, d, 1);
+        jm.nsrc = 1; jm.bias = t->BM; jm.act = 1;
+        jm.mul = t->head_mul; jm.ld_mul = 64;
+        fc.head = &jm;
+    }
+    EqdChainJob cj[EQD_CHAIN_MAXJOBS];
+    const int nj = node_fwd_chain(fc, cj);
+    return eqd_launch_rowchain(cj, nj, t->rows, (hipStream_t)stream);
 }

@@ -1015,8 +1015,26 @@ static int chain_resident_on() {
     const char* f = eqd_tunable("EQD_CHAIN_RESIDENT");
     return !(f && f[0] == '0' && f[1] == 0);
 }
-static bool cr_fwd_eligible(const EqdChainJob* jobs, int njobs, int rows) {
-    if (!chain_resident_on() || njobs != 2 || rows <= 0 || eqd_row_tiles(rows) != 1 || eqd_rowchain_blocks(rows) > eqd_num_cus()) return false;
+// The carrying forms (NP = 5: the next layer's five node projections behind node_mlp.4, NP = 1: the head's mlp_h_mean_ROT
+// behind the last layer's) are taken when the list continues with exactly such jobs on job 1's tile; EQD_CHAIN_RESIDENT_PROJ=0
+// keeps the two-job body and the projections' own launches.
+static int chain_resident_proj_on() {
+    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT_PROJ");
+    return chain_resident_on() && !(f && f[0] == '0' && f[1] == 0);
+}
+// may a forward chain over `rows` rows run on the resident body at all (what does not depend on the job list)?
+static bool cr_fwd_rows_ok(int rows) {
+    const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");      // (a forced register budget means: this experiment wants k_rowchain)
+    return chain_resident_on() && !(oc && oc[0]) && rows > 0 && eqd_row_tiles(rows) == 1 && eqd_rowchain_blocks(rows) <= eqd_num_cus();
+}
+// the driver asks BEFORE it builds the list: would a 64-wide layer's chain over `rows` rows carry projection jobs?
+// (rw_mode: a forced EQD_ROWWAVE hands eligible chains to k_rowwave / k_rowres before this body is asked)
+int eqd_chain_carries_proj(int rows) { return chain_resident_proj_on() && cr_fwd_rows_ok(rows) && rw_mode(rows) == 0; }
+// matches the list structurally and fills the kernel's compact argument; np: carried jobs (0, 1, 5)
+static bool crf_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResFwdArg& A, int& np) {
+    if (njobs < 2 || !cr_fwd_rows_ok(rows)) return false;
+    np = njobs - 2;
+    if (np != 0 && !((np == 1 || np == 5) && chain_resident_proj_on())) return false;
     const EqdChainJob &C0 = jobs[0], &C1 = jobs[1];
     const EqdLinJob &J0 = C0.lin, &J1 = C1.lin;
     if (C0.type != 0 || C1.type != 0 || J0.bf16 || J1.bf16 || J0.rows != rows || J1.rows != rows) return false;
@@ -1026,13 +1044,36 @@ static bool cr_fwd_eligible(const EqdChainJob* jobs, int njobs, int rows) {
         if (!S.X || !S.W || S.mask || S.w_cs != 1 || C0.src_local[s] >= 0) return false;
         if (s < 3 ? S.K != 64 : (S.K <= 64 || S.K > 80)) return false;
     }
-    if (J1.M != 64 || J1.nsrc != 1 || C1.src_local[0] != 0 || C1.out_local >= 0 || J1.ln_g || J1.mul || J1.pre_ln) return false;
+    if (J1.M != 64 || J1.nsrc != 1 || C1.src_local[0] != 0 || J1.ln_g || J1.mul || J1.pre_ln) return false;
+    if (np == 0 ? C1.out_local >= 0 : C1.out_local < 0) return false;
     if (J1.s[0].K != 64 || !J1.s[0].W || J1.s[0].mask || J1.s[0].w_cs != 1) return false;
+    memset(&A, 0, sizeof(A));
+    A.rows = rows; A.K3 = J0.s[3].K;
+    for (int s = 0; s < 4; ++s) A.s[s] = CrfSrc{J0.s[s].X, J0.s[s].W, J0.s[s].ldx, J0.s[s].w_rs};
+    A.act0 = J0.act; A.slope0 = J0.slope; A.ln_eps = J0.ln_eps; A.alpha0 = J0.alpha; A.beta0 = J0.beta;
+    A.bias0 = J0.bias; A.ln_g = J0.ln_g; A.ln_b = J0.ln_b; A.mul0 = J0.mul; A.ld_mul0 = J0.ld_mul;
+    A.pre_ln = J0.pre_ln; A.ld_pre = J0.ld_pre; A.Y0 = J0.Y; A.ldy0 = J0.ldy; A.Yb0 = J0.Yb; A.ldyb0 = J0.ldyb;
+    A.W1 = J1.s[0].W; A.w1_rs = J1.s[0].w_rs; A.bias1 = J1.bias; A.R1 = J1.R; A.ldr1 = J1.ldr;
+    A.act1 = J1.act; A.slope1 = J1.slope; A.alpha1 = J1.alpha; A.beta1 = J1.beta;
+    A.Y1 = J1.Y; A.ldy1 = J1.ldy; A.Yb1 = J1.Yb; A.ldyb1 = J1.ldyb;
+    for (int j = 0; j < np; ++j) {      // a carried job: one 64 x 64 product on job 1's tile, k_linear_simple's kind
+        const EqdChainJob& C = jobs[2 + j];
+        const EqdLinJob& J = C.lin;
+        if (C.type != 0 || J.bf16 || J.rows != rows || J.M != 64 || J.nsrc != 1 || C.src_local[0] != C1.out_local ||
+            C.out_local >= 0 || J.s[0].K != 64 || !J.s[0].W || J.s[0].w_cs != 1 || J.s[0].mask || J.ln_g || J.ln_b || J.R ||
+            J.pre_ln || J.Yb || J.pad_to != 0 || !J.Y || (J.mul && np != 1))
+            return false;
+        A.p[j] = CrfProj{J.s[0].W, J.bias, J.Y, J.s[0].w_rs, J.ldy, J.act, J.slope, J.alpha, J.beta};
+        if (J.mul) { A.pmul = J.mul; A.ld_pmul = J.ld_mul; }
+    }
     return true;
 }
 static std::atomic<long long> g_chain_resident_launches{0};
 // how many row chains this process has launched on the resident-weights body (tests: which body ran)
 extern "C" long long eqd_chain_resident_launches(void) { return g_chain_resident_launches.load(); }
+static std::atomic<long long> g_chain_resident_proj_launches{0};
+// ... and how many of them carried projection jobs (NP = 1 or 5)
+extern "C" long long eqd_chain_resident_proj_launches(void) { return g_chain_resident_proj_launches.load(); }
 
 // k_rowchain_res_bwd (eqd_chainres_bwd_inl.h): the backward chain of a 64-wide layer under the same conditions.  Taken for
 // exactly the two job lists eqd_model_backward builds with cross_msgs on - [dh of the layer above,] alpha dH Wn2, LayerNorm
@@ -1151,13 +1192,19 @@ int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_
     }
     if (partial_rows) *partial_rows = eqd_rowchain_blocks(rows);
     {
-        const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");      // (a forced register budget means: this experiment wants k_rowchain)
-        if (!(oc && oc[0]) && cr_fwd_eligible(jobs, njobs, rows)) {
-            hipLaunchKernelGGL(k_rowchain_res_fwd, dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
+        ChainResFwdArg farg;
+        int np = 0;
+        if (crf_pack(jobs, njobs, rows, farg, np)) {
+            const dim3 grid(eqd_rowchain_blocks(rows));
+            if (np == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_fwd<5>), grid, dim3(EQD_BLOCK), 0, st, farg);
+            else if (np == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_fwd<1>), grid, dim3(EQD_BLOCK), 0, st, farg);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_fwd<0>), grid, dim3(EQD_BLOCK), 0, st, farg);
             g_chain_resident_launches.fetch_add(1);
+            if (np) g_chain_resident_proj_launches.fetch_add(1);
             return eqd_check_launch("k_rowchain");
         }
         ChainResBwdArg barg;
+        const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");      // (a forced register budget means: this experiment wants k_rowchain)
         if (!(oc && oc[0]) && crb_pack(jobs, njobs, rows, barg)) {
             if (njobs == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_bwd<true>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, barg);
             else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_bwd<false>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, barg);

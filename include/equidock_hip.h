@@ -57,7 +57,7 @@ int eqd_tile_edges(void);
 int eqd_is_simulator(void);
 /* The EQD_* environment switches that select kernel forms for tests and A/B measurements (EQD_FUSE_FWD, EQD_FUSE_GATHER,
  * EQD_ATT_SPLIT, EQD_ATT_BWD_SPLIT, EQD_ATT_LB, EQD_ATT_LB_NB, EQD_ATT_DS, EQD_ATT_QDS_NB, EQD_ROWWAVE, EQD_ROW_TILES,
- * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_CHAIN_RESIDENT_BWD, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
+ * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_CHAIN_RESIDENT_BWD, EQD_CHAIN_RESIDENT_PROJ, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
  * agree on the forms they run.  A caller that changes one of them afterwards calls this to make the library forget its
  * snapshot (nothing in the reference corresponds to it). */
 void eqd_tunables_reload(void);
@@ -97,6 +97,30 @@ typedef struct EqdNodeChainBwdTest {
     float* dh0acc;
 } EqdNodeChainBwdTest;
 int eqd_selftest_node_chain_bwd(const EqdNodeChainBwdTest* t, int* partial_rows /* host */, void* stream);
+/* Test aid: of the launches counted by eqd_chain_resident_launches(), those that carried further jobs on the tile of h[l+1]
+ * (k_rowchain_res_fwd<5>: the next layer's five node projections P, Q, q, k, v; k_rowchain_res_fwd<1>: the head's
+ * mlp_h_mean_ROT behind the last layer) instead of leaving them to a k_linear launch of their own.  Small batches (no more
+ * row tiles than CUs), fp32, cross messages, 64-wide layers; EQD_CHAIN_RESIDENT_PROJ=0 keeps the two-job body and the
+ * separate launches (read once per process like the switches listed above), EQD_CHAIN_RESIDENT=0 turns off every resident body. */
+long long eqd_chain_resident_proj_launches(void);
+/* Test aid: ONE forward node chain of a 64-wide layer on the caller's buffers, built by the list builders eqd_model_forward
+ * uses: node_mlp.0 on [h, aggr_msg, aggr_cross, h0] ([rows][64] each, h0 [rows][d0]; Wn1 [64][d0 + 192]) -> LeakyReLU
+ * [* drop_mul] -> y_act -> LayerNorm -> a1n -> node_mlp.4 (Wn2 [64][64]) + skip -> h_out; form 5: then the next layer's
+ * projections of h_out (W1 [64][128]: P from columns 0 .. 63, Q from 64 .. 127 with bias B1; q, k with LeakyReLU, v) in the same
+ * launch, form 1: the head's hm = LeakyReLU(h_out WM^T + BM) [* head_mul]; form 0: neither.  The model keeps these buffers
+ * inside its state arena; here a test can put guard rows behind each. */
+typedef struct EqdNodeChainFwdTest {
+    int32_t rows, d0, form;
+    float skip_weight_h, slope, ln_eps;
+    const float* h; const float* aggr_msg; const float* aggr_cross; const float* h0;
+    const float* Wn1; const float* Bn1; const float* ln_g; const float* ln_b; const float* Wn2; const float* Bn2;
+    const float* drop_mul;      /* or NULL */
+    float* a1n; float* y_act; float* h_out;
+    const float* W1; const float* B1; const float* WQ; const float* WK; const float* WV;      /* form 5 */
+    float* P; float* Q; float* qa; float* ka; float* va;
+    const float* WM; const float* BM; const float* head_mul /* or NULL */; float* hm;           /* form 1 */
+} EqdNodeChainFwdTest;
+int eqd_selftest_node_chain_fwd(const EqdNodeChainFwdTest* t, void* stream);
 /* Test aid: one 256-thread workgroup runs the library's cross-lane helpers (DPP moves, v_permlane{16,32}_swap) on in256
  * [256] beside the plain ds_bpermute forms, and the guard-free exponentials of the softmax kernels beside expf / exp2f;
  * mismatch [4] (device ints, zeroed by the caller) receives the number of differing (lane, check) pairs of the exchanges [0],
@@ -237,6 +261,13 @@ int eqd_model_check(const EqdModelDesc* m, const EqdGraph* g);
  * latter as 'hv_iegmn_out' / 'x_iegmn_out', rigid_docking_model.py:507-510) inside the `saved` buffer of a forward. */
 int eqd_model_layer_state(const EqdModelDesc* m, const EqdGraph* g, const void* saved, size_t saved_bytes, int layer,
                           const float** h, int* h_width, const float** x);
+
+/* Test / debug aid: pointers to the node-level tensors of layer `layer` (0 .. n_layers - 1) inside the `saved` buffer of an
+ * fp32 forward: out[0 .. 6] = P, Q [n_nodes][64] (the split first edge Linear), attention q, k, v [n_nodes][*d_att] (q, k, v are
+ * NULL without cross_msgs), a1n [n_nodes][*d_in] (node_mlp.0 .. LayerNorm) and hm [n_nodes][64] (mlp_h_mean_ROT, the same
+ * pointer for every layer).  EQD_ERR_UNSUPPORTED in bf16 storage mode. */
+int eqd_model_node_state(const EqdModelDesc* m, const EqdGraph* g, const void* saved, size_t saved_bytes, int layer,
+                         const float** out /* [7] */, int* d_in, int* d_att);
 
 /* Test / debug aid: the LeakyReLU branch decisions of the forward whose state is in `saved`, one byte per element
  * (1 = pre-activation > 0, i.e. derivative 1; 0 = derivative lrelu_slope) - exactly the masks eqd_model_backward applies.
