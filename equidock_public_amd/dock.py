@@ -31,6 +31,9 @@ DOCK_METER_ABI = 1
 METER_COLS = 8             # EQD_DOCK_METER_COLS
 DOCK_QUALITY_ABI = 1
 QUALITY_COLS = 16          # EQD_DOCK_QUALITY_COLS
+DOCK_EMD_ABI = 1
+EMD_MAX_NODES = 2048       # EQD_DOCK_EMD_MAX_NODES
+EMD_RESIDENT_CELLS = 8192  # EQD_DOCK_EMD_RESIDENT_CELLS
 
 _dock = None
 _dock_is_sim = False
@@ -77,6 +80,14 @@ def _declare(lib):
     lib.eqd_dock_quality_eval.restype = C.c_int
     lib.eqd_dock_quality_eval.argtypes = ([C.c_int] + [C.c_void_p] * 12 + [C.c_double] * 3 + [C.c_int, C.c_void_p, C.c_void_p,
                                                                                              C.c_size_t, C.c_void_p])
+    lib.eqd_dock_emd_abi.restype = C.c_int
+    lib.eqd_dock_emd_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_emd_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    lib.eqd_dock_emd_init.restype = C.c_int
+    lib.eqd_dock_emd_init.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_emd_solve.restype = C.c_int
+    lib.eqd_dock_emd_solve.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]
 
 
 def _bind(path):
@@ -91,6 +102,8 @@ def _bind(path):
         raise _lib.EquidockHipError(f"{path}: dock meter ABI {lib.eqd_dock_meter_abi()} != {DOCK_METER_ABI}")
     if lib.eqd_dock_quality_abi() != DOCK_QUALITY_ABI:
         raise _lib.EquidockHipError(f"{path}: dock quality ABI {lib.eqd_dock_quality_abi()} != {DOCK_QUALITY_ABI}")
+    if lib.eqd_dock_emd_abi() != DOCK_EMD_ABI:
+        raise _lib.EquidockHipError(f"{path}: dock EMD ABI {lib.eqd_dock_emd_abi()} != {DOCK_EMD_ABI}")
     _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
     return lib
 
@@ -334,6 +347,68 @@ class DeviceMeter:
         if arr.size == 0:
             return float('nan'), float('nan')
         return f(arr), np.std(arr)
+
+
+# ---- batched exact transport plans -----------------------------------------------------------------------------------
+def emd_resident_enabled():
+    """EQD_DOCK_EMD_RESIDENT=0 forces the general body of the device solver (cost read from global memory, flow in the
+    workspace) for every problem; same plans either way."""
+    return os.environ.get('EQD_DOCK_EMD_RESIDENT', '1') != '0'
+
+
+class EmdPlan:
+    """Workspace and status buffer of eqd_dock_emd_solve for one ragged batch of transport problems with uniform marginals
+    (problem p: counts[p] sources, n_snk sinks): created and initialised once (init copies the offset table and waits for
+    that copy), then `solve` only enqueues ONE launch - it can be captured into a hipGraph."""
+
+    def __init__(self, counts, n_snk, dev):
+        lib = load_dock_library()
+        self.counts = [int(c) for c in counts]
+        if not self.counts or min(self.counts) < 0:
+            raise ValueError(f"EmdPlan: counts = {self.counts} (need >= 1 problem, no negative count)")
+        self.n, self.K, self.dev = len(self.counts), int(n_snk), torch.device(dev)
+        _require_device(torch.empty(0, device=self.dev), 'transport problems')
+        self.off = _offsets(self.counts)
+        self.rows = int(self.off[-1])
+        self._off = self.off.ctypes.data_as(C.c_void_p)
+        self.wsb = lib.eqd_dock_emd_workspace_bytes(self.n, self._off, self.K)
+        if self.wsb == 0:
+            check(2)
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        self.status = torch.zeros(self.n, dtype=torch.int32, device=self.dev)
+        with _lib.device_guard(self.dev):
+            check(lib.eqd_dock_emd_init(self.n, self._off, self.K, _lib.ptr(self.ws), C.c_size_t(self.wsb), _stream(self.dev)))
+
+    def solve(self, cost, plan, resident=None):
+        """Enqueue the solve on the current stream: cost, plan [sum(counts)][n_snk] fp32 contiguous, bit-identical to
+        losses.emd_uniform_host's plans.  No synchronisation, no allocation, no copy; `status` is written by the launch."""
+        for t, what in ((cost, 'cost'), (plan, 'plan')):
+            _require_device(t, what)
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (self.rows, self.K):
+                raise ValueError(f"EmdPlan.solve: {what} must be a contiguous float32 [{self.rows}, {self.K}] tensor, got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+        resident = emd_resident_enabled() if resident is None else bool(resident)
+        with _lib.device_guard(self.dev):
+            check(_dock.eqd_dock_emd_solve(self.n, self._off, self.K, _lib.ptr(cost), _lib.ptr(plan), _lib.ptr(self.status),
+                                           int(resident), _lib.ptr(self.ws), C.c_size_t(self.wsb), _stream(self.dev)))
+        return plan
+
+    def failed(self):
+        """Indices of the problems of the latest solve whose status is non-zero (ONE download; it synchronises)."""
+        return [int(i) for i in np.nonzero(self.status.cpu().numpy())[0]]
+
+
+def emd_uniform_batch(cost, counts, resident=None):
+    """losses.emd_uniform_host on the device: exact plans of a ragged batch of transport problems with uniform marginals.
+    cost: device float32 [sum(counts), K].  Returns (plan [sum(counts), K] float32, status [len(counts)] int32) on the
+    device, without synchronising beyond the workspace's init; a failed problem (status 1) has a NaN plan."""
+    cost = _require_device(cost.detach().to(torch.float32).contiguous(), 'cost')
+    if cost.dim() != 2 or int(sum(int(c) for c in counts)) != cost.shape[0]:
+        raise ValueError("counts do not add up to the rows of cost")
+    ep = EmdPlan(counts, cost.shape[1], cost.device)
+    plan = torch.empty_like(cost)
+    ep.solve(cost, plan, resident=resident)
+    return plan, ep.status
 
 
 # ---- batched docking quality: fnat, LRMSD, iRMSD(bb), DockQ, clashes ------------------------------------------------------

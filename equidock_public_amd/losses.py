@@ -8,7 +8,8 @@ reference's Python loop with an (n_l x n_r) torch matrix per pair and term.
 `compute_body_intersection_loss` keeps the reference's name and signature for one pair.  The pocket OT term
 (compute_ot_emd -> ot.emd, src/utils/ot_utils.py:22-29) is `pocket_ot_loss` below: cost matrices, the plan-weighted sum
 and its gradient on the device for the whole batch (eqd_pocket_ot_*), the exact transport plans from the host solver of
-libequidock_host.so (eqd_host_emd_uniform, in place of POT's ot.emd) with ONE device<->host round trip per batch.
+libequidock_host.so (eqd_host_emd_uniform, in place of POT's ot.emd) with ONE device<->host round trip per batch - or, with
+solver='device', from the device solver of libequidock_dock.so (eqd_dock_emd_solve: the same plans bit for bit, no round trip).
 No CPU fallback: tensors must be on the GPU.
 """
 import ctypes as C
@@ -186,7 +187,7 @@ def emd_uniform_host(cost, counts, n_threads=0):
 class _PocketOT(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, Yl, Yr, pl, pr, off_dev, counts, n_threads):
+    def forward(ctx, Yl, Yr, pl, pr, off_dev, counts, n_threads, emd_plan=None):
         lib = _lib.load_library()
         dev = Yl.device
         B, K = Yl.shape[0], Yl.shape[1]
@@ -199,9 +200,14 @@ class _PocketOT(torch.autograd.Function):
         with _lib.device_guard(dev):
             _lib.check(lib.eqd_pocket_ot_cost(B, K, _lib.ptr(off_dev), _lib.ptr(pl), _lib.ptr(pr), _lib.ptr(Yl_),
                                               _lib.ptr(Yr_), _lib.ptr(cost), st))
-        # the one D->H / H->D round trip of the batch (the reference has one per pair, src/utils/ot_utils.py:23, 27)
-        plan_host, _ = emd_uniform_host(cost.cpu(), counts, n_threads)
-        plan = plan_host.to(dev, non_blocking=False)
+        if emd_plan is not None:
+            # the device solver (dock.EmdPlan): one more launch on the same stream, no synchronisation, no download
+            plan = torch.empty_like(cost)
+            emd_plan.solve(cost, plan)
+        else:
+            # the one D->H / H->D round trip of the batch (the reference has one per pair, src/utils/ot_utils.py:23, 27)
+            plan_host, _ = emd_uniform_host(cost.cpu(), counts, n_threads)
+            plan = plan_host.to(dev, non_blocking=False)
         with _lib.device_guard(dev):
             _lib.check(lib.eqd_pocket_ot_fwd(B, K, _lib.ptr(off_dev), _lib.ptr(plan), _lib.ptr(cost), _lib.ptr(ot), st))
         ctx.save_for_backward(Yl_, Yr_, pl, pr, off_dev, plan)
@@ -212,7 +218,7 @@ class _PocketOT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_ot, _d_plan):
         if d_ot is None:
-            return (None,) * 7
+            return (None,) * 8
         lib = _lib.load_library()
         Yl, Yr, pl, pr, off_dev, plan = ctx.saved_tensors
         dev = Yl.device
@@ -223,18 +229,26 @@ class _PocketOT(torch.autograd.Function):
             _lib.check(lib.eqd_pocket_ot_bwd(B, K, _lib.ptr(off_dev), _lib.ptr(pl), _lib.ptr(pr), _lib.ptr(Yl), _lib.ptr(Yr),
                                              _lib.ptr(plan), _lib.ptr(g), _lib.ptr(dYl), _lib.ptr(dYr),
                                              _lib.stream_ptr(dev)))
-        return dYl, dYr, None, None, None, None, None
+        return dYl, dYr, None, None, None, None, None, None
 
 
 def pocket_ot_loss(keypts_ligand, keypts_receptor, pocket_coors_ligand_list, pocket_coors_receptor_list, n_threads=0,
-                   return_plan=False):
+                   return_plan=False, solver='host', emd_plan=None):
     """The pocket OT term of every pair of a batch (src/train.py:117-129): ot[p] = compute_ot_emd(
     compute_sq_dist_mat(pocket_lig_p, Y_lig_p) + compute_sq_dist_mat(pocket_rec_p, Y_rec_p))[0].
 
     keypts_*: [B, K, 3] device tensors (the model's 2nd / 3rd outputs, stacked; gradients flow to them);
     pocket_coors_*_list: per pair (n_pocket_p, 3) tensors, matched rows (src/utils/db5_data.py pocket_coors).
     Cost matrices, sum(plan * cost) and its gradient run on the device for the whole batch; the exact plans come from the
-    host solver on worker threads (ONE device<->host round trip per batch).  Returns ot [B] (and the plans)."""
+    host solver on worker threads (ONE device<->host round trip per batch).  solver='device': the plans come from the
+    device solver instead (dock.EmdPlan, libequidock_dock.so: bit-identical plans) and the call neither synchronises nor
+    downloads; `emd_plan` is a dock.EmdPlan of these counts to reuse - without one the call creates it, and that
+    creation uploads the offset table and waits for that one copy.  A problem the device solver could not solve
+    (non-finite costs) has a NaN plan and a NaN ot; EmdPlan.failed() names it.  Returns ot [B] (and the plans)."""
+    if solver not in ('host', 'device'):
+        raise ValueError(f"pocket_ot_loss: solver = {solver!r} (expected 'host' or 'device')")
+    if emd_plan is not None and solver != 'device':
+        raise ValueError("pocket_ot_loss: emd_plan is for solver='device'")
     dev = keypts_ligand.device
     counts = [int(t.shape[0]) for t in pocket_coors_ligand_list]
     if counts != [int(t.shape[0]) for t in pocket_coors_receptor_list] or len(counts) != keypts_ligand.shape[0]:
@@ -243,7 +257,15 @@ def pocket_ot_loss(keypts_ligand, keypts_receptor, pocket_coors_ligand_list, poc
     pr = torch.cat([t.reshape(-1, 3) for t in pocket_coors_receptor_list]).to(dev, torch.float32).contiguous()
     _lib.require_device(pl, 'pocket coordinates')
     off = torch.tensor([0] + list(torch.tensor(counts).cumsum(0).tolist()), dtype=torch.int32).to(dev)
-    ot, plan = _PocketOT.apply(keypts_ligand, keypts_receptor, pl, pr, off, counts, int(n_threads))
+    if solver == 'device':
+        from . import dock
+        K = int(keypts_ligand.shape[1])
+        if emd_plan is None:
+            emd_plan = dock.EmdPlan(counts, K, dev)
+        elif emd_plan.counts != counts or emd_plan.K != K:
+            raise ValueError(f"pocket_ot_loss: the EmdPlan holds counts {emd_plan.counts} x {emd_plan.K}, the batch "
+                             f"{counts} x {K}")
+    ot, plan = _PocketOT.apply(keypts_ligand, keypts_receptor, pl, pr, off, counts, int(n_threads), emd_plan)
     return (ot, plan) if return_plan else ot
 
 

@@ -24,6 +24,13 @@ src/train.py:137-140, no interface) into a fixed [B][8] buffer, and every step()
 device-to-device copy of that buffer into the meter - no further host join.  One difference from the reference: it samples
 a random tenth of the training pairs (src/train.py:136), this meters every pair of every step it is attached to; the
 caller attaches the meter (an evaluation epoch, a sampled training step) or not.  Without `meter` nothing new is launched.
+
+`TrainStep(ot_solver='device')` takes the plans from the device solver of libequidock_dock.so (eqd_dock_emd_solve, dock.EmdPlan:
+bit-identical to the host solver's) instead: forward, cost matrices, solve, pair terms, OT value and gradient, backward - all
+on ONE stream with no host join.  `capture()` records ONE single-stream graph, `step()` is one replay, `step_unfused()` the
+same launches enqueued from the host; the pinned buffers and both copies do not exist, there is no gap to time
+(`last_ot_exposed_ms()` raises), and `ot_failed()` - which synchronises: for the caller's epoch end - names the problems the
+solver could not solve (non-finite costs; their plans, and with them the loss, are NaN).  The default stays 'host'.
 """
 import ctypes as C
 
@@ -35,12 +42,16 @@ from . import _lib, losses
 class TrainStep:
 
     def __init__(self, net, batch, lig_target, rec, pocket_lig_list, pocket_rec_list, w_ot=1.0, w_int=10.0, sigma=25.0,
-                 surface_ct=10.0, reducer=None, n_threads=0, allreduce=False, meter=None):
+                 surface_ct=10.0, reducer=None, n_threads=0, allreduce=False, meter=None, ot_solver='host'):
         """lig_target [n_lig, 3] / rec [n_rec, 3]: bound coordinates in the batch's node order (src/train.py:114, 131);
         pocket_*_list: per pair (n_pocket, 3), matched rows; weights / sigma / surface_ct: src/utils/args.py:64-70;
         reducer: parallel.FlatGradAllReduce of `net` (gradients accumulate in its flat buffer); allreduce: issue the
         collective at the end of the backward (a process group must exist); meter: a dock.DeviceMeter that receives the
-        [B][8] RMSD rows of every step (see the module docstring)."""
+        [B][8] RMSD rows of every step (see the module docstring); ot_solver: 'host' (libequidock_host.so between the
+        graphs) or 'device' (libequidock_dock.so inside the one graph)."""
+        if ot_solver not in ('host', 'device'):
+            raise ValueError(f"TrainStep: ot_solver = {ot_solver!r} (expected 'host' or 'device')")
+        self.ot_solver = ot_solver
         from .parallel import FlatGradAllReduce
         self.net, self.batch = net, batch
         self.packed = batch.pack()
@@ -69,9 +80,14 @@ class TrainStep:
         self.cost = torch.empty(rows, K, **f32)
         self.plan = torch.empty(rows, K, **f32)
         pin = dev.type == 'cuda'      # (the simulator of the tests runs this class on host tensors: no pinning, no events)
-        self.cost_host = torch.empty(rows, K, dtype=torch.float32, pin_memory=pin)
-        self.plan_host = torch.empty(rows, K, dtype=torch.float32, pin_memory=pin)
-        self.values_host = torch.empty(B, dtype=torch.float64)
+        if ot_solver == 'host':
+            self.cost_host = torch.empty(rows, K, dtype=torch.float32, pin_memory=pin)
+            self.plan_host = torch.empty(rows, K, dtype=torch.float32, pin_memory=pin)
+            self.values_host = torch.empty(B, dtype=torch.float64)
+            self._emd = None
+        else:                         # workspace, offset table and status buffer now, outside any capture
+            from . import dock
+            self._emd = dock.EmdPlan(counts, K, dev)
         self.mse, self.inter, self.ot = torch.empty(B, **f32), torch.empty(B, **f32), torch.zeros(B, **f32)
         self.s_lig, self.s_rec = torch.empty(self.packed.n_lig, **f32), torch.empty(self.packed.n_rec, **f32)
         self.d_lig = torch.empty(self.packed.n_lig, 3, **f32)
@@ -82,7 +98,8 @@ class TrainStep:
         self.loss = torch.zeros((), **f32)
         self._graphs = None
         self._outs = None
-        self._ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if dev.type == 'cuda' else None
+        self._ev = ([torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                    if dev.type == 'cuda' and ot_solver == 'host' else None)
         self._exposed = []
         self.meter, self._meter_muted = meter, False
         if meter is not None:       # workspace and item table now, outside any capture
@@ -100,7 +117,10 @@ class TrainStep:
             _lib.check(lib.eqd_pocket_ot_cost(self.B, self.K, _lib.ptr(self.off), _lib.ptr(self.pl), _lib.ptr(self.pr),
                                               _lib.ptr(Yl.detach()), _lib.ptr(Yr.detach()), _lib.ptr(self.cost),
                                               _lib.stream_ptr(self.dev)))
-        self.cost_host.copy_(self.cost, non_blocking=True)
+        if self._emd is None:
+            self.cost_host.copy_(self.cost, non_blocking=True)
+        else:
+            self._emd.solve(self.cost, self.plan)
 
     def _pair_terms(self):
         lib = _lib.load_library()
@@ -168,17 +188,27 @@ class TrainStep:
         self._metered()
         return self.loss
 
+    def _device_step(self):
+        """ot_solver='device': the whole step enqueued on the current stream (the solve rides behind the cost matrices)"""
+        self._forward_and_cost()
+        self._pair_terms()
+        self._ot_and_backward()
+
     def _metered(self):
         if self.meter is not None and not self._meter_muted:
             self.meter.append_rows(self.meter_rows)
 
     def step_unfused(self):
         """the same step with every launch enqueued from the host (no graphs)"""
+        if self._emd is not None:
+            self._device_step()
+            self._metered()
+            return self.loss
         return self._join(self._forward_and_cost, self._pair_terms, self._ot_and_backward)
 
     def capture(self):
         """capture the three device parts into hipGraphs that share one memory pool (the forward's saved state lives in it
-        until the backward graph has consumed it)"""
+        until the backward graph has consumed it); with ot_solver='device' the whole step into ONE graph"""
         torch.cuda.synchronize()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -189,6 +219,13 @@ class TrainStep:
         self._meter_muted = False
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if self._emd is not None:
+            g1 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g1, capture_error_mode='thread_local'):
+                self._device_step()
+            self._graphs = (g1,)
+            torch.cuda.synchronize()
+            return self
         gf, gm, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(gf, capture_error_mode='thread_local'):
             self._forward_and_cost()
@@ -205,21 +242,38 @@ class TrainStep:
     def step(self):
         if self._graphs is None:
             return self.step_unfused()
+        if self._emd is not None:
+            self._graphs[0].replay()
+            self._metered()
+            return self.loss
         gf, gm, gb = self._graphs
         return self._join(gf.replay, gm.replay, gb.replay)
 
     def last_ot_exposed_ms(self):
         """GPU-timeline gap between the end of graph M and the start of graph B of the last step (synchronises)"""
+        if self._emd is not None:
+            raise _lib.EquidockHipError("last_ot_exposed_ms: with ot_solver='device' the transport solve is a launch inside "
+                                        "the step's one graph - there is no host gap to time")
         self._ev[1].synchronize()
         return self._ev[0].elapsed_time(self._ev[1])
 
-    def step_eager(self):
+    def ot_failed(self):
+        """ot_solver='device': indices of the pairs whose transport problem the latest step could not solve (ONE download;
+        it SYNCHRONISES - for the caller's epoch end, not for every step)"""
+        if self._emd is None:
+            raise _lib.EquidockHipError("ot_failed: with ot_solver='host' a failed solve raises inside the step")
+        return self._emd.failed()
+
+    def step_eager(self, solver=None):
         """the same arithmetic through the autograd wrappers of losses.py (pair_losses, pocket_ot_loss): one blocking
-        round trip inside pocket_ot_loss, no graphs - the form tests compare with the oracle"""
+        round trip inside pocket_ot_loss (none with solver='device'; default: the step's ot_solver), no graphs - the form
+        tests compare with the oracle"""
+        solver = self.ot_solver if solver is None else solver
         self.reducer.zero()
         lig, Yl, Yr, T, b = self.net.forward_batched(self.batch)
         mse, inter = losses.pair_losses(self.batch, lig, self.lig_target, self.rec, self.sigma, self.ct)
-        ot = losses.pocket_ot_loss(Yl, Yr, self.pl_list, self.pr_list, n_threads=self.n_threads)
+        ot = losses.pocket_ot_loss(Yl, Yr, self.pl_list, self.pr_list, n_threads=self.n_threads, solver=solver,
+                                   emd_plan=self._emd if solver == 'device' else None)
         loss = mse.mean() + self.w_ot * ot.mean() + self.w_int * inter.mean()
         loss.backward()
         if self.allreduce:

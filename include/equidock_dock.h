@@ -201,6 +201,46 @@ EQD_DOCK_API int eqd_dock_quality_eval(int n_complex, const int32_t* lig_atom_of
                                        double interface_cutoff, double clash_cutoff, int prune, double* quality,
                                        void* workspace, size_t ws_bytes, void* stream);
 
+/*
+ * Batched exact transport plans: the solver call of the pocket OT term, src/utils/ot_utils.py:22-29 (POT's
+ * ot.emd(a, b, M) with uniform a = 1/n, b = 1/m), for P problems in ONE launch - the call that replaces the host solver
+ * eqd_host_emd_uniform (csrc_host/eqd_host_emd.cpp) and the device <-> host round trip around it.  The algorithm is the
+ * host solver's restated operation for operation (successive shortest paths, fp64 from the fp32 costs): a problem's plan
+ * is bit-identical to the host solver's, alone, in any batch, at any position and from run to run.
+ *
+ * Layout (that of eqd_pocket_ot_*): the row blocks of all problems, one after another.
+ *   src_off [P + 1]  HOST int32, src_off[0] = 0, non-decreasing: problem p = rows src_off[p] .. src_off[p + 1] - 1 (its n
+ *                    sources); a problem of 0 rows is allowed and writes no plan row, as on the host
+ *   n_snk            m >= 1 sinks (columns), the same for every problem; n + m <= EQD_DOCK_EMD_MAX_NODES per problem
+ *   cost, plan [sum n][n_snk] fp32; every row of a solved plan sums to 1 / n, every column to 1 / m
+ *   status [P] int32: 0 solved; 1 the problem failed - no sink with demand could be reached (non-finite costs: the host
+ *                    solver returns NaN there) or a loop bound was overrun - and its plan rows are NaN.  Every loop of
+ *                    the kernel has a bound computed from n and m: it ends on any input.
+ * One workgroup of one wave per problem.  Cost and flow matrices sit in LDS while n * m <=
+ * EQD_DOCK_EMD_RESIDENT_CELLS (the resident body), above it the flow sits in the workspace (the general body);
+ * `resident` == 0 forces the general body for every problem.  Same operations, same bits.
+ * Sequence: workspace_bytes -> init (once per set of offsets) -> solve (any number of times).
+ */
+#define EQD_DOCK_EMD_ABI 1
+#define EQD_DOCK_EMD_MAX_NODES 2048
+#define EQD_DOCK_EMD_RESIDENT_CELLS 8192
+EQD_DOCK_API int eqd_dock_emd_abi(void);
+
+/* Workspace of a batch with these host offsets; 0 when they are invalid (eqd_dock_last_error says why). */
+EQD_DOCK_API size_t eqd_dock_emd_workspace_bytes(int n_problems, const int32_t* src_off, int n_snk);
+
+/* Validates the sizes (EQD_ERR_NULL; EQD_ERR_SHAPE for offsets that do not start at 0 or decrease, n_snk < 1 and a problem
+ * of more than EQD_DOCK_EMD_MAX_NODES nodes) and writes the offset table into the workspace (a host-to-device copy; this
+ * call waits for that copy). */
+EQD_DOCK_API int eqd_dock_emd_init(int n_problems, const int32_t* src_off, int n_snk, void* workspace, size_t ws_bytes,
+                                   void* stream);
+
+/* Enqueues the solve (one launch of n_problems workgroups) on a workspace prepared by eqd_dock_emd_init with the same
+ * offsets.  No synchronisation, no allocation, no host-device copy: the call can be captured into a hipGraph.  The same
+ * validation as init; nothing is launched when it fails. */
+EQD_DOCK_API int eqd_dock_emd_solve(int n_problems, const int32_t* src_off, int n_snk, const float* cost, float* plan,
+                                    int32_t* status, int resident, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
