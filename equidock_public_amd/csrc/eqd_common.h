@@ -536,7 +536,10 @@ struct EqdChainArg {
     int njobs;
 };
 // partial_rows (optional): rows of LayerNorm-backward partial sums the launch wrote (= its workgroups)
-int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_t st, int* partial_rows = nullptr);
+// wide_ok: the list may run on the wide resident body (eqd_chainres_wide_inl.h); the model driver passes cross_msgs - without
+// cross messages layer 0's list has the same shape (a zero-filled aggr_cross source) and stays on the general body
+int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_t st, int* partial_rows = nullptr,
+                        bool wide_ok = true);
 size_t eqd_atb_batch_partial_bytes(int rows);
 // the end of the backward riding in the weight-gradient launches (eqd_node_kernels.hip)
 int eqd_atb_tail_wanted(const EqdLinJob* dh0_job, int n_atb_jobs);

@@ -980,7 +980,7 @@ extern "C" int eqd_model_forward(const EqdModelDesc* m, const EqdGraph* g, const
         }
         EqdChainJob cj[EQD_CHAIN_MAXJOBS];
         const int nj = node_fwd_chain(fc, cj);
-        RC(eqd_launch_rowchain(cj, nj, N, st));
+        RC(eqd_launch_rowchain(cj, nj, N, st, nullptr, m->cross_msgs != 0));
     }
     if (!head_in_chain) RC(eqd_linear(&jm, 1, st));
     // ---- keypoint head ----------------------------------------------------------------------------------

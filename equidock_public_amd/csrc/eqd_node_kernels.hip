@@ -9,6 +9,7 @@
 #include "eqd_rowres_inl.h"
 #include "eqd_rowres80_inl.h"
 #include "eqd_chainres_inl.h"
+#include "eqd_chainres_wide_inl.h"
 #include "eqd_gather_inl.h"
 
 #include <atomic>
@@ -1075,6 +1076,45 @@ static std::atomic<long long> g_chain_resident_proj_launches{0};
 // ... and how many of them carried projection jobs (NP = 1 or 5)
 extern "C" long long eqd_chain_resident_proj_launches(void) { return g_chain_resident_proj_launches.load(); }
 
+// k_rowchain_res_fwd_wide (eqd_chainres_wide_inl.h): the forward chain of the 69-wide first layer under the same conditions -
+// the two-job list node_fwd_chain builds for layer 0 with cross messages on (eqd_node_update_fwd at 69 x 69 builds it too).
+// Exactly d = d0 = 69: the remainder images of the body are laid out for 5 columns beyond 64.  EQD_CHAIN_RESIDENT=0 turns
+// it off with the other resident bodies, EQD_CHAIN_RESIDENT_WIDE=0 alone.  A forced EQD_ROWWAVE keeps the list on k_rowchain
+// as well.  (Layer 0's BACKWARD chain has no resident form: it stays on k_rowchain.)
+static int chain_resident_wide_on() {
+    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT_WIDE");
+    return chain_resident_on() && !(f && f[0] == '0' && f[1] == 0);
+}
+static bool crw_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResWideArg& A) {
+    if (njobs != 2 || !chain_resident_wide_on() || !cr_fwd_rows_ok(rows) || rw_mode(rows) != 0) return false;
+    const EqdChainJob &C0 = jobs[0], &C1 = jobs[1];
+    const EqdLinJob &J0 = C0.lin, &J1 = C1.lin;
+    if (C0.type != 0 || C1.type != 0 || J0.bf16 || J1.bf16 || J0.rows != rows || J1.rows != rows) return false;
+    if (J0.M != 69 || J0.nsrc != 4 || C0.out_local != 0 || !J0.ln_g || !J0.ln_b || J0.R || J0.Yb || J0.pad_to != 0) return false;
+    for (int s = 0; s < 4; ++s) {
+        const EqdLinSrc& S = J0.s[s];
+        if (!S.X || !S.W || S.mask || S.w_cs != 1 || C0.src_local[s] >= 0) return false;
+        if (S.K != (s == 1 ? 64 : 69) || S.ldx < S.K) return false;
+    }
+    if (J1.M != 64 || J1.nsrc != 1 || C1.src_local[0] != 0 || C1.out_local >= 0 || J1.ln_g || J1.ln_b || J1.mul || J1.pre_ln ||
+        J1.R || J1.Yb || J1.pad_to != 0 || !J1.Y)
+        return false;
+    if (J1.s[0].K != 69 || !J1.s[0].W || J1.s[0].mask || J1.s[0].w_cs != 1) return false;
+    memset(&A, 0, sizeof(A));
+    A.rows = rows; A.M = J0.M;
+    for (int s = 0; s < 4; ++s) A.s[s] = CrfSrc{J0.s[s].X, J0.s[s].W, J0.s[s].ldx, J0.s[s].w_rs};
+    A.act0 = J0.act; A.slope0 = J0.slope; A.ln_eps = J0.ln_eps; A.alpha0 = J0.alpha; A.beta0 = J0.beta;
+    A.bias0 = J0.bias; A.ln_g = J0.ln_g; A.ln_b = J0.ln_b; A.mul0 = J0.mul; A.ld_mul0 = J0.ld_mul;
+    A.pre_ln = J0.pre_ln; A.ld_pre = J0.ld_pre; A.Y0 = J0.Y; A.ldy0 = J0.ldy;
+    A.W1 = J1.s[0].W; A.w1_rs = J1.s[0].w_rs; A.bias1 = J1.bias;
+    A.act1 = J1.act; A.slope1 = J1.slope; A.alpha1 = J1.alpha; A.beta1 = J1.beta;
+    A.Y1 = J1.Y; A.ldy1 = J1.ldy;
+    return true;
+}
+static std::atomic<long long> g_chain_resident_wide_launches{0};
+// how many row chains ran on the wide resident body (never counted by the three counters above: those are 64-wide layers)
+extern "C" long long eqd_chain_resident_wide_launches(void) { return g_chain_resident_wide_launches.load(); }
+
 // k_rowchain_res_bwd (eqd_chainres_bwd_inl.h): the backward chain of a 64-wide layer under the same conditions.  Taken for
 // exactly the two job lists eqd_model_backward builds with cross_msgs on - [dh of the layer above,] alpha dH Wn2, LayerNorm
 // backward, dz times three ADJACENT 64-column blocks of Wn1 - matched structurally; crb_pack fills the kernel's compact
@@ -1149,7 +1189,7 @@ static bool crb_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResBwdAr
 static std::atomic<long long> g_chain_resident_bwd_launches{0};
 extern "C" long long eqd_chain_resident_bwd_launches(void) { return g_chain_resident_bwd_launches.load(); }
 
-int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_t st, int* partial_rows) {
+int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_t st, int* partial_rows, bool wide_ok) {
     if (njobs <= 0 || njobs > EQD_CHAIN_MAXJOBS) {
         eqd_set_error("eqd_launch_rowchain: %d jobs (1..%d)", njobs, EQD_CHAIN_MAXJOBS);
         return EQD_ERR_SHAPE;
@@ -1201,6 +1241,12 @@ int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_
             else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_fwd<0>), grid, dim3(EQD_BLOCK), 0, st, farg);
             g_chain_resident_launches.fetch_add(1);
             if (np) g_chain_resident_proj_launches.fetch_add(1);
+            return eqd_check_launch("k_rowchain");
+        }
+        ChainResWideArg warg;
+        if (wide_ok && crw_pack(jobs, njobs, rows, warg)) {
+            hipLaunchKernelGGL(k_rowchain_res_fwd_wide, dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, warg);
+            g_chain_resident_wide_launches.fetch_add(1);
             return eqd_check_launch("k_rowchain");
         }
         ChainResBwdArg barg;

@@ -57,7 +57,7 @@ int eqd_tile_edges(void);
 int eqd_is_simulator(void);
 /* The EQD_* environment switches that select kernel forms for tests and A/B measurements (EQD_FUSE_FWD, EQD_FUSE_GATHER,
  * EQD_ATT_SPLIT, EQD_ATT_BWD_SPLIT, EQD_ATT_LB, EQD_ATT_LB_NB, EQD_ATT_DS, EQD_ATT_QDS_NB, EQD_ROWWAVE, EQD_ROW_TILES,
- * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_CHAIN_RESIDENT_BWD, EQD_CHAIN_RESIDENT_PROJ, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
+ * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_CHAIN_RESIDENT_BWD, EQD_CHAIN_RESIDENT_PROJ, EQD_CHAIN_RESIDENT_WIDE, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
  * agree on the forms they run.  A caller that changes one of them afterwards calls this to make the library forget its
  * snapshot (nothing in the reference corresponds to it). */
 void eqd_tunables_reload(void);
@@ -103,6 +103,13 @@ int eqd_selftest_node_chain_bwd(const EqdNodeChainBwdTest* t, int* partial_rows 
  * row tiles than CUs), fp32, cross messages, 64-wide layers; EQD_CHAIN_RESIDENT_PROJ=0 keeps the two-job body and the
  * separate launches (read once per process like the switches listed above), EQD_CHAIN_RESIDENT=0 turns off every resident body. */
 long long eqd_chain_resident_proj_launches(void);
+/* Test aid: how many row chains ran on the wide resident body (k_rowchain_res_fwd_wide: the forward node chain of the 69-wide
+ * FIRST layer - node_mlp.0 with 69 outputs on sources of 69, 64, 69, 69 columns, LayerNorm over 69 features, node_mlp.4 with
+ * K = 69 - under the conditions of the bodies above; eqd_node_update_fwd at 69 x 69 with cross messages builds the same
+ * list).  The three counters above never count it: they keep meaning 64-wide layers.  EQD_CHAIN_RESIDENT_WIDE=0 keeps
+ * k_rowchain for this chain alone (read once per process like the switches listed above), EQD_CHAIN_RESIDENT=0 turns off
+ * every resident body. */
+long long eqd_chain_resident_wide_launches(void);
 /* Test aid: ONE forward node chain of a 64-wide layer on the caller's buffers, built by the list builders eqd_model_forward
  * uses: node_mlp.0 on [h, aggr_msg, aggr_cross, h0] ([rows][64] each, h0 [rows][d0]; Wn1 [64][d0 + 192]) -> LeakyReLU
  * [* drop_mul] -> y_act -> LayerNorm -> a1n -> node_mlp.4 (Wn2 [64][64]) + skip -> h_out; form 5: then the next layer's
