@@ -847,8 +847,7 @@ static int attention_bwd_f32(const EqdGraph* g, int d, const float* q, const flo
     const bool al = aligned16(q) && aligned16(k) && aligned16(v) && aligned16(d_out) && aligned16(out);
     // d = 64: half blocks (two workgroups per CU, see k_attn_bwd) - config C +2.3 %, E +0.9 %, B unchanged;
     // EQD_ATT_BWD_SPLIT=0 keeps 32-row blocks (tests)
-    const char* hb = eqd_tunable("EQD_ATT_BWD_SPLIT");
-    const bool half = !(hb && hb[0] == '0' && hb[1] == 0) && g->n_att_items % 8 == 0;
+    const bool half = eqd_switch_on("EQD_ATT_BWD_SPLIT") && g->n_att_items % 8 == 0;
     if (d == 64 && al && half) return attn_launch_bwd<4, true, 1>(g, d, q, k, v, out, lse, d_out, dq, dk, dv, delta, st, qk_slope);
     if (d == 64 && al) return attn_launch_bwd<4, true, 2>(g, d, q, k, v, out, lse, d_out, dq, dk, dv, delta, st, qk_slope);
     if (d == 80 && al) return attn_launch_bwd<5, true, 2>(g, d, q, k, v, out, lse, d_out, dq, dk, dv, delta, st, qk_slope);
@@ -858,10 +857,7 @@ static int attention_bwd_f32(const EqdGraph* g, int d, const float* q, const flo
 
 // bf16 mode, d = 64: the streamed tiles live in LDS as bf16 (eqd_attn_lb_inl.h) unless EQD_ATT_LB=0 (the first bf16 version:
 // fp32 tiles in LDS, rounded per MFMA operand; kept for the 80-wide first layer, tests and A/B measurements)
-static bool att_lds_bf16() {
-    const char* f = eqd_tunable("EQD_ATT_LB");
-    return !(f && f[0] == '0' && f[1] == 0);
-}
+static bool att_lds_bf16() { return eqd_switch_on("EQD_ATT_LB"); }
 
 // ---- bf16 mode: the four contractions of the forward (Q K^T, P V) and the ten of the backward run on
 // v_mfma_f32_16x16x16_bf16 - inputs rounded to bf16 when the MFMA operands are formed, fp32 accumulate; logits, softmax
@@ -960,10 +956,7 @@ int eqd_launch_attention_bwd_act(const EqdGraph* g, int d, const float* q, const
 // one after the other
 int eqd_attention_bwd_gather_fused(const EqdGraph* g, int d, const float* q, const float* k, const float* v, const float* out,
                                    const float* d_out, bool bf16) {
-    const char* f = eqd_tunable("EQD_FUSE_GATHER");
-    if (f && f[0] == '0' && f[1] == 0) return 0;
-    const char* hb = eqd_tunable("EQD_ATT_BWD_SPLIT");
-    if (hb && hb[0] == '0' && hb[1] == 0) return 0;
+    if (!eqd_switch_on("EQD_FUSE_GATHER") || !eqd_switch_on("EQD_ATT_BWD_SPLIT")) return 0;
     if (d == 80 && g->n_att_items > 0)      // the first layer's merged backward (one workgroup per item and pass)
         return aligned16(q) && aligned16(k) && aligned16(v) && aligned16(d_out) && aligned16(out);
     if (d != 64 || g->n_att_items <= 0 || g->n_att_items % 8 != 0) return 0;
@@ -999,8 +992,7 @@ int eqd_attention_ds_wanted(const EqdGraph* g, int d, bool bf16) {
         const char* nb2 = eqd_tunable("EQD_ATT_LB_NB");
         if (!att_lds_bf16() || (nb2 && nb2[0] == '2')) return 0;
     }
-    const char* hb = eqd_tunable("EQD_ATT_BWD_SPLIT");
-    if (hb && hb[0] == '0' && hb[1] == 0) return 0;
+    if (!eqd_switch_on("EQD_ATT_BWD_SPLIT")) return 0;
     const char* f = eqd_tunable("EQD_ATT_DS");
     if (f && (f[0] == '0' || f[0] == '1') && f[1] == 0) return f[0] == '1';
     return g->n_att_items > eqd_num_cus();

@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/equidock_hip.h"
 
@@ -472,6 +473,7 @@ __device__ __forceinline__ void wave_lds_fence() {
 void eqd_set_error(const char* fmt, ...);
 int eqd_check_launch(const char* what);
 const char* eqd_tunable(const char* name);   // EQD_* experiment switch, snapshotted once per process (eqd_tunables_reload)
+bool eqd_switch_on(const char* name);        // an on/off EQD_* switch: true unless the variable is exactly "0"
 int eqd_num_cus();   // compute units of the current HIP device (256 on MI355X; queried once per device)
 
 static inline size_t eqd_align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
@@ -535,6 +537,12 @@ struct EqdChainArg {
     EqdChainJob j[EQD_CHAIN_MAXJOBS];
     int njobs;
 };
+// an empty chain job: all zero, every source global, the result not kept in LDS
+static inline void eqd_chain_job_clear(EqdChainJob& C) {
+    memset(&C, 0, sizeof(C));
+    for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
+    C.out_local = -1;
+}
 // partial_rows (optional): rows of LayerNorm-backward partial sums the launch wrote (= its workgroups)
 // wide_ok: the list may run on the wide resident body (eqd_chainres_wide_inl.h); the model driver passes cross_msgs - without
 // cross messages layer 0's list has the same shape (a zero-filled aggr_cross source) and stays on the general body

@@ -217,13 +217,11 @@ int node_pre_jobs(const NodePre& n, const float* hsrc, int loc, EqdChainJob* cj)
     int nj = 0;
     auto add = [&](float* Y, int M, int ldy, const float* Wp, int w_rs, const float* bias, int act) {
         EqdChainJob& C = cj[nj++];
-        memset(&C, 0, sizeof(C));
+        eqd_chain_job_clear(C);
         C.lin = lin_job(n.N, M, Y, ldy, n.slope, n.eps);
         lin_src(C.lin, 0, hsrc, n.d, n.d, Wp, w_rs, 1);
         C.lin.nsrc = 1; C.lin.bias = bias; C.lin.act = act;
-        for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
         C.src_local[0] = loc;
-        C.out_local = -1;
     };
     add(n.P, 64, 64, n.W1, n.ldw1, nullptr, 0);
     add(n.Q, 64, 64, n.W1 + n.d, n.ldw1, n.B1, 0);
@@ -243,7 +241,9 @@ int node_pre_jobs(const NodePre& n, const float* hsrc, int loc, EqdChainJob* cj)
 // The forward row chain of one layer's node update, as eqd_model_forward launches it: node_mlp([h, aggr_msg, aggr_cross, h0])
 // -> LeakyReLU [-> dropout] -> LayerNorm (a1n, LDS tile 0) -> node_mlp.4 (+ skip) = h_out [-> LDS tile 1 -> the carried jobs:
 // the next layer's projections (`next`) or the head's mlp_h_mean_ROT (`head`)].  Returns the number of jobs (2, 3, 4 or 7).
-// (Also built by eqd_selftest_node_chain_fwd: the same lists on test buffers.)
+// (Also built by eqd_selftest_node_chain_fwd, the same lists on test buffers, and by eqd_node_update_fwd.)
+// aggr_cross == NULL (the operator without cross messages): job 0 has the three sources h, aggr_msg, h0.
+// The bf16 row strides (ldyb) are set whether or not the bf16 outputs exist; no body reads them under Yb == NULL.
 struct NodeFwdChain {
     int N, d, da, d0, dh, ldn, ld_a1n;
     float slope, eps, skip;
@@ -256,11 +256,12 @@ struct NodeFwdChain {
 int node_fwd_chain(const NodeFwdChain& c, EqdChainJob* cj) {
     const int d = c.d;
     EqdLinJob j1 = lin_job(c.N, d, c.a1n, d, c.slope, c.eps);
-    lin_src(j1, 0, c.h, d, d, c.Wn1, c.ldn, 1);
-    lin_src(j1, 1, c.aggr_msg, 64, 64, c.Wn1 + d, c.ldn, 1);
-    lin_src(j1, 2, c.aggr_cross, c.da, d, c.Wn1 + d + 64, c.ldn, 1);
-    lin_src(j1, 3, c.h0, c.d0, c.d0, c.Wn1 + 2 * d + 64, c.ldn, 1);
-    j1.nsrc = 4; j1.bias = c.Bn1; j1.act = 1; j1.ln_g = c.ln_g; j1.ln_b = c.ln_b;
+    int ns = 0;
+    lin_src(j1, ns++, c.h, d, d, c.Wn1, c.ldn, 1);
+    lin_src(j1, ns++, c.aggr_msg, 64, 64, c.Wn1 + d, c.ldn, 1);
+    if (c.aggr_cross) lin_src(j1, ns++, c.aggr_cross, c.da, d, c.Wn1 + d + 64, c.ldn, 1);
+    lin_src(j1, ns++, c.h0, c.d0, c.d0, c.Wn1 + 2 * d + 64, c.ldn, 1);
+    j1.nsrc = ns; j1.bias = c.Bn1; j1.act = 1; j1.ln_g = c.ln_g; j1.ln_b = c.ln_b;
     j1.pre_ln = c.y_act; j1.ld_pre = d;
     j1.Yb = c.a1n_b; j1.ldyb = c.ld_a1n;               // bf16 storage mode: a1n is saved as bf16 (Y = NULL)
     j1.mul = c.drop_mul; j1.ld_mul = d;                // node_mlp.1 (Dropout) in training mode
@@ -272,11 +273,8 @@ int node_fwd_chain(const NodeFwdChain& c, EqdChainJob* cj) {
         j2.alpha = c.skip; j2.beta = 1.f - c.skip; j2.R = c.h; j2.ldr = d;
     }
     // one launch: the LayerNorm output stays in LDS for node_mlp.4
-    memset(cj, 0, 2 * sizeof(EqdChainJob));
-    for (int k = 0; k < 2; ++k) {
-        for (int i = 0; i < EQD_MAX_SRC; ++i) cj[k].src_local[i] = -1;
-        cj[k].out_local = -1;
-    }
+    eqd_chain_job_clear(cj[0]);
+    eqd_chain_job_clear(cj[1]);
     cj[0].lin = j1; cj[0].out_local = 0;
     cj[1].lin = j2; cj[1].src_local[0] = 0;
     int nj = 2;
@@ -286,11 +284,9 @@ int node_fwd_chain(const NodeFwdChain& c, EqdChainJob* cj) {
     } else if (c.head) {
         cj[1].out_local = 1;
         EqdChainJob& C = cj[nj++];
-        memset(&C, 0, sizeof(C));
+        eqd_chain_job_clear(C);
         C.lin = *c.head;
-        for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
         C.src_local[0] = 1;
-        C.out_local = -1;
     }
     return nj;
 }
@@ -298,32 +294,29 @@ int node_fwd_chain(const NodeFwdChain& c, EqdChainJob* cj) {
 // The backward row chain of one layer, as eqd_model_backward launches it: [dh of the layer above (kept as LDS tile 2) ->]
 // da1n = alpha dH Wn2 (tile 0) -> LeakyReLU / LayerNorm backward (dz, tile 1, the ln_part rows) -> dz times the column
 // blocks of Wn1: d aggr_msg, d aggr_cross (cross messages only), the embedding columns of d h0 accumulated over the layers.
-// Returns the number of jobs written to cj (<= 6).  (Also built by eqd_selftest_node_chain_bwd: the same lists on test buffers.)
+// Returns the number of jobs written to cj (<= 6).  (Also built by eqd_selftest_node_chain_bwd, the same lists on test
+// buffers, and by eqd_node_update_bwd.)
+// d_aggr_cross == NULL (no cross messages): no d aggr_cross job.  d_h != NULL (the operator): one more job, LAST,
+// d_h = dz Wn1[:, :d] plus the skip connection's (1 - s) dHout - a list the resident backward body declines.
 struct NodeBwdChain {
     int N, d, da, d0, d_emb, ldn, dh_width;
     float slope, eps, alpha;
-    bool cross;
     const EqdLinJob* dh;      // the dh job of the layer above, or NULL: the last layer, which also initialises dh0acc
     const float *dHout, *Wn2, *Wn1, *y_act, *ln_g, *drop_mul;
-    float *dz, *lnp, *d_aggr_msg, *d_aggr_cross, *dh0acc;
+    float *dz, *lnp, *d_aggr_msg, *d_aggr_cross, *dh0acc, *d_h;
 };
 int node_bwd_chain(const NodeBwdChain& c, EqdChainJob* cj) {
     int nj = 0;
-    auto clear = [&](EqdChainJob& C) {
-        memset(&C, 0, sizeof(C));
-        for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
-        C.out_local = -1;
-    };
     const bool fused_dh = c.dh != nullptr;
     if (fused_dh) {
         EqdChainJob& C = cj[nj++];
-        clear(C);
+        eqd_chain_job_clear(C);
         C.lin = *c.dh;
         C.out_local = 2;
     }
     {
         EqdChainJob& C = cj[nj++];
-        clear(C);
+        eqd_chain_job_clear(C);
         C.lin = lin_job(c.N, c.d, nullptr, c.d, c.slope, c.eps);
         lin_src(C.lin, 0, c.dHout, c.dh_width, c.dh_width, c.Wn2, 1, c.d);
         C.lin.nsrc = 1; C.lin.alpha = c.alpha;
@@ -332,7 +325,7 @@ int node_bwd_chain(const NodeBwdChain& c, EqdChainJob* cj) {
     }
     {
         EqdChainJob& C = cj[nj++];
-        clear(C);
+        eqd_chain_job_clear(C);
         C.type = 1;
         C.lin = lin_job(c.N, c.d, c.dz, c.d, c.slope, c.eps);
         lin_src(C.lin, 0, c.y_act, c.d, c.d, nullptr, 0, 0);
@@ -344,7 +337,7 @@ int node_bwd_chain(const NodeBwdChain& c, EqdChainJob* cj) {
     }
     auto dx_job = [&](float* Y, int M, int ldy, int coff) -> EqdChainJob& {
         EqdChainJob& C = cj[nj++];
-        clear(C);
+        eqd_chain_job_clear(C);
         C.lin = lin_job(c.N, M, Y, ldy, c.slope, c.eps);
         lin_src(C.lin, 0, c.dz, c.d, c.d, c.Wn1 + coff, 1, c.ldn);
         C.lin.nsrc = 1;
@@ -354,12 +347,17 @@ int node_bwd_chain(const NodeBwdChain& c, EqdChainJob* cj) {
     dx_job(c.d_aggr_msg, 64, 64, c.d);
     // (padding columns of d aggr_cross when da != d: the job writes them as zeros, EqdLinJob.pad_to - they meet zeros in V,
     //  but must not be NaN bit patterns left in the scratch buffer)
-    if (c.cross) dx_job(c.d_aggr_cross, c.d, c.da, c.d + 64).lin.pad_to = c.da != c.d ? c.da : 0;
-    // only the embedding columns of d h0 are ever read (k_embed_bwd: the trailing node features are inputs), so the
-    // job computes d_emb of the d0 columns: a 64-wide job instead of a 69-wide one (the general body)
+    if (c.d_aggr_cross) dx_job(c.d_aggr_cross, c.d, c.da, c.d + 64).lin.pad_to = c.da != c.d ? c.da : 0;
+    // the model: only the embedding columns of d h0 are ever read (k_embed_bwd: the trailing node features are inputs), so
+    // the job computes d_emb of the d0 columns: a 64-wide job instead of a 69-wide one (the general body)
     EqdChainJob& C5 = dx_job(c.dh0acc, c.d_emb, c.d0, 2 * c.d + 64);
     if (fused_dh) {      // the last layer (processed first) initialises the accumulator
         C5.lin.R = c.dh0acc; C5.lin.ldr = c.d0; C5.lin.beta = 1.f;
+    }
+    if (c.d_h) {
+        EqdChainJob& C = dx_job(c.d_h, c.d, c.d, 0);
+        // (alpha is the skip weight s exactly when the layer has a skip connection)
+        if (c.d == c.dh_width) { C.lin.R = c.dHout; C.lin.ldr = c.dh_width; C.lin.beta = 1.f - c.alpha; }
     }
     return nj;
 }
@@ -1160,8 +1158,6 @@ extern "C" int eqd_model_backward(const EqdModelDesc* m, const EqdGraph* g, cons
         const float alpha = skip ? m->skip_weight_h : 1.f;
         const int ldn = D.ldwn(l);
         const int da = D.d_att(l);
-        // (padding columns of d aggr_cross when da != d: the chain's job writes them as zeros, EqdLinJob.pad_to - they meet
-        //  zeros in V, but must not be NaN bit patterns left in the scratch buffer)
         float *dz = W.dz_all + l * NS, *dq = W.dq_all + l * NS, *dk = W.dk_all + l * NS, *dv = W.dv_all + l * NS;
         float *dP = W.dP_all + l * NP, *dQ = W.dQ_all + l * NP;
         float* dHout = dHof(l + 1);
@@ -1175,11 +1171,11 @@ extern "C" int eqd_model_backward(const EqdModelDesc* m, const EqdGraph* g, cons
             NodeBwdChain nc;
             nc.N = N; nc.d = d; nc.da = da; nc.d0 = D.d0; nc.d_emb = m->d_emb; nc.ldn = ldn; nc.dh_width = D.dh;
             nc.slope = slope; nc.eps = eps; nc.alpha = alpha;
-            nc.cross = m->cross_msgs != 0;
             nc.dh = l < D.L - 1 ? &dhj : nullptr;
             nc.dHout = dHout; nc.Wn2 = p[P_WN2]; nc.Wn1 = p[P_WN1]; nc.y_act = Ls.y_act; nc.ln_g = p[P_NLG];
             nc.drop_mul = drop_node(D, drop, l);
-            nc.dz = dz; nc.lnp = lnp; nc.d_aggr_msg = W.d_aggr_msg; nc.d_aggr_cross = W.d_aggr_cross; nc.dh0acc = W.dh0acc;
+            nc.dz = dz; nc.lnp = lnp; nc.d_aggr_msg = W.d_aggr_msg; nc.d_aggr_cross = m->cross_msgs ? W.d_aggr_cross : nullptr;
+            nc.dh0acc = W.dh0acc; nc.d_h = nullptr;
             const int nj = node_bwd_chain(nc, cj);
             int nb = 0;      // partial rows of the LayerNorm-backward sums = workgroups of whichever kernel took the chain
             RC(eqd_launch_rowchain(cj, nj, N, st, &nb));
@@ -1310,31 +1306,18 @@ extern "C" int eqd_node_update_fwd(int rows, const EqdNodeUpdateParams* p, const
     }
     if (rows == 0) return EQD_OK;
     g_bf16_mode = p->bf16 ? 1 : 0;
-    const int d = p->d_in, ldn = p->d0 + 2 * d + 64;
-    EqdLinJob j1 = lin_job(rows, d, a1n, d, p->slope, p->ln_eps);
-    int ns = 0;
-    lin_src(j1, ns++, h, d, d, p->Wn1, ldn, 1);
-    lin_src(j1, ns++, aggr_msg, 64, 64, p->Wn1 + d, ldn, 1);
-    if (aggr_cross) lin_src(j1, ns++, aggr_cross, p->ld_cross, d, p->Wn1 + d + 64, ldn, 1);      // NULL: cross_msgs off (zeros)
-    lin_src(j1, ns++, h0, p->d0, p->d0, p->Wn1 + 2 * d + 64, ldn, 1);
-    j1.nsrc = ns; j1.bias = p->bn1; j1.act = 1; j1.ln_g = p->ln_g; j1.ln_b = p->ln_b;
-    j1.pre_ln = y_act; j1.ld_pre = d;
-    j1.mul = p->drop_mul; j1.ld_mul = d;
-    EqdLinJob j2 = lin_job(rows, p->d_out, h_out, p->d_out, p->slope, p->ln_eps);
-    lin_src(j2, 0, a1n, d, d, p->Wn2, d, 1);
-    j2.nsrc = 1; j2.bias = p->bn2;
-    if (d == p->d_out) {
-        j2.alpha = p->skip_weight_h; j2.beta = 1.f - p->skip_weight_h; j2.R = h; j2.ldr = d;
-    }
+    const int d = p->d_in;
+    NodeFwdChain fc;
+    fc.N = rows; fc.d = d; fc.da = p->ld_cross; fc.d0 = p->d0; fc.dh = p->d_out; fc.ldn = p->d0 + 2 * d + 64; fc.ld_a1n = 0;
+    fc.slope = p->slope; fc.eps = p->ln_eps; fc.skip = p->skip_weight_h;
+    fc.h = h; fc.aggr_msg = aggr_msg; fc.aggr_cross = aggr_cross; fc.h0 = h0;      // aggr_cross NULL: cross_msgs off (zeros)
+    fc.Wn1 = p->Wn1; fc.Bn1 = p->bn1; fc.ln_g = p->ln_g; fc.ln_b = p->ln_b; fc.Wn2 = p->Wn2; fc.Bn2 = p->bn2;
+    fc.drop_mul = p->drop_mul;
+    fc.a1n = a1n; fc.y_act = y_act; fc.h_out = h_out; fc.a1n_b = nullptr; fc.hb_out = nullptr;
+    fc.next = nullptr; fc.head = nullptr;
     EqdChainJob cj[2];
-    memset(cj, 0, sizeof(cj));
-    for (int k = 0; k < 2; ++k) {
-        for (int i = 0; i < EQD_MAX_SRC; ++i) cj[k].src_local[i] = -1;
-        cj[k].out_local = -1;
-    }
-    cj[0].lin = j1; cj[0].out_local = 0;
-    cj[1].lin = j2; cj[1].src_local[0] = 0;
-    return eqd_launch_rowchain(cj, 2, rows, (hipStream_t)stream);
+    const int nj = node_fwd_chain(fc, cj);
+    return eqd_launch_rowchain(cj, nj, rows, (hipStream_t)stream);
 }
 
 extern "C" size_t eqd_node_update_bwd_workspace_bytes(int rows, const EqdNodeUpdateParams* p) {
@@ -1365,54 +1348,18 @@ extern "C" int eqd_node_update_bwd(int rows, const EqdNodeUpdateParams* p, const
         eqd_set_error("eqd_node_update_bwd: workspace too small (%zu needed)", A.off + 256);
         return EQD_ERR_WORKSPACE;
     }
-    const int d = p->d_in, ldn = p->d0 + 2 * d + 64;
-    const bool skip = d == p->d_out;
-    const float alpha = skip ? p->skip_weight_h : 1.f;
+    const int d = p->d_in;
     // ONE row chain: d a1n = alpha d_h_out Wn2 -> LeakyReLU / LayerNorm backward (dz) -> dz times the four column blocks
-    // of Wn1 (the gradient w.r.t. h also takes the skip connection's (1 - s) d_h_out)
+    // of Wn1, d h0 at its full width (the gradient w.r.t. h also takes the skip connection's (1 - s) d_h_out)
+    NodeBwdChain nc;
+    nc.N = rows; nc.d = d; nc.da = p->ld_cross; nc.d0 = p->d0; nc.d_emb = p->d0; nc.ldn = p->d0 + 2 * d + 64; nc.dh_width = p->d_out;
+    nc.slope = p->slope; nc.eps = p->ln_eps; nc.alpha = d == p->d_out ? p->skip_weight_h : 1.f;
+    nc.dh = nullptr;
+    nc.dHout = d_h_out; nc.Wn2 = p->Wn2; nc.Wn1 = p->Wn1; nc.y_act = y_act; nc.ln_g = p->ln_g; nc.drop_mul = p->drop_mul;
+    nc.dz = W.dz; nc.lnp = W.ln_part; nc.d_aggr_msg = d_aggr_msg; nc.d_aggr_cross = aggr_cross ? d_aggr_cross : nullptr;
+    nc.dh0acc = d_h0; nc.d_h = d_h;
     EqdChainJob cj[EQD_CHAIN_MAXJOBS];
-    int nj = 0;
-    auto clear = [&](EqdChainJob& C) {
-        memset(&C, 0, sizeof(C));
-        for (int i = 0; i < EQD_MAX_SRC; ++i) C.src_local[i] = -1;
-        C.out_local = -1;
-    };
-    {
-        EqdChainJob& C = cj[nj++];
-        clear(C);
-        C.lin = lin_job(rows, d, nullptr, d, p->slope, p->ln_eps);
-        lin_src(C.lin, 0, d_h_out, p->d_out, p->d_out, p->Wn2, 1, d);
-        C.lin.nsrc = 1; C.lin.alpha = alpha;
-        C.out_local = 0;
-    }
-    {
-        EqdChainJob& C = cj[nj++];
-        clear(C);
-        C.type = 1;
-        C.lin = lin_job(rows, d, W.dz, d, p->slope, p->ln_eps);
-        lin_src(C.lin, 0, y_act, d, d, nullptr, 0, 0);
-        C.lin.nsrc = 1; C.lin.ln_g = p->ln_g;
-        C.lin.mul = p->drop_mul; C.lin.ld_mul = d;
-        C.src_local[0] = 0;
-        C.out_local = 1;
-        C.aux = W.ln_part;
-    }
-    auto dx_job = [&](float* Y, int M, int ldy, int coff) -> EqdChainJob& {
-        EqdChainJob& C = cj[nj++];
-        clear(C);
-        C.lin = lin_job(rows, M, Y, ldy, p->slope, p->ln_eps);
-        lin_src(C.lin, 0, W.dz, d, d, p->Wn1 + coff, 1, ldn);
-        C.lin.nsrc = 1;
-        C.src_local[0] = 1;
-        return C;
-    };
-    dx_job(d_aggr_msg, 64, 64, d);
-    if (aggr_cross) dx_job(d_aggr_cross, d, p->ld_cross, d + 64).lin.pad_to = p->ld_cross != d ? p->ld_cross : 0;
-    dx_job(d_h0, p->d0, p->d0, 2 * d + 64);
-    {
-        EqdChainJob& C = dx_job(d_h, d, d, 0);
-        if (skip) { C.lin.R = d_h_out; C.lin.ldr = p->d_out; C.lin.beta = 1.f - p->skip_weight_h; }
-    }
+    const int nj = node_bwd_chain(nc, cj);
     int nb = 0;
     RC(eqd_launch_rowchain(cj, nj, rows, st, &nb));
     EqdRedSeg segs[2] = {{W.ln_part, nb, 256, d, grads->dln_g, 0, 0, 0}, {W.ln_part + 128, nb, 256, d, grads->dln_b, 0, 0, 0}};
@@ -1454,11 +1401,11 @@ extern "C" int eqd_selftest_node_chain_bwd(const EqdNodeChainBwdTest* t, int* pa
     NodeBwdChain nc;
     nc.N = t->rows; nc.d = d; nc.da = d; nc.d0 = t->d0; nc.d_emb = 64; nc.ldn = t->d0 + 2 * d + 64; nc.dh_width = d;
     nc.slope = t->slope; nc.eps = t->ln_eps; nc.alpha = t->skip_weight_h;
-    nc.cross = true;
     nc.dh = t->with_dh ? &dhj : nullptr;
     nc.dHout = t->with_dh ? t->dH : t->dH_above;
     nc.Wn2 = t->Wn2; nc.Wn1 = t->Wn1; nc.y_act = t->y_act; nc.ln_g = t->ln_g; nc.drop_mul = t->drop_mul;
     nc.dz = t->dz; nc.lnp = t->ln_part; nc.d_aggr_msg = t->d_aggr_msg; nc.d_aggr_cross = t->d_aggr_cross; nc.dh0acc = t->dh0acc;
+    nc.d_h = nullptr;
     EqdChainJob cj[8];
     const int nj = node_bwd_chain(nc, cj);
     return eqd_launch_rowchain(cj, nj, t->rows, (hipStream_t)stream, partial_rows);

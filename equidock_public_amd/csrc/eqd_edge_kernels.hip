@@ -1172,13 +1172,10 @@ extern "C" int eqd_edge_message_fwd(const EqdGraph* g, const EqdEdgeParams* p, c
 
 // 1 if eqd_edge_attn_fwd will take the fused launch for this graph / width / mode (else it issues the two launches)
 int eqd_edge_attn_fused(const EqdGraph* g, const EqdEdgeParams* p, int d_att, const float* q, const float* k, const float* v) {
-    const char* f = eqd_tunable("EQD_FUSE_FWD");
-    if (f && f[0] == '0' && f[1] == 0) return 0;
+    if (!eqd_switch_on("EQD_FUSE_FWD")) return 0;
     if (p->bf16 || (d_att != 64 && d_att != 80) || g->n_tiles <= 0 || g->n_att_items <= 0) return 0;
-    if (d_att == 80) {      // the first layer's form (round 5); EQD_FUSE_FWD80=0 keeps the two launches
-        const char* f8 = eqd_tunable("EQD_FUSE_FWD80");
-        if (f8 && f8[0] == '0' && f8[1] == 0) return 0;
-    }
+    // the first layer's form (round 5); EQD_FUSE_FWD80=0 keeps the two launches
+    if (d_att == 80 && !eqd_switch_on("EQD_FUSE_FWD80")) return 0;
     if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) != 0) return 0;
     const int n_edge = edge_grid(g->n_tiles, FWD_WAVES, 1);
     return n_edge + g->n_att_items <= eqd_num_cus();

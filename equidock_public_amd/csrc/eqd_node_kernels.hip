@@ -73,6 +73,10 @@ const char* eqd_tunable(const char* name) {
     memcpy(out, hit->value, sizeof(hit->value));
     return out;
 }
+bool eqd_switch_on(const char* name) {
+    const char* f = eqd_tunable(name);
+    return !(f && f[0] == '0' && f[1] == 0);
+}
 extern "C" void eqd_tunables_reload(void) {
     std::lock_guard<std::mutex> lk(g_tun_mu);
     g_tun_n = 0;
@@ -370,8 +374,7 @@ __global__ __launch_bounds__(EQD_BLOCK, 4) void k_linear_simple(LinJobsArg jobs)
 }
 // may every job of the launch run on k_linear_simple?  (EQD_LINEAR_SIMPLE=0 keeps k_linear: tests, A/B runs)
 static bool lin_simple_eligible(const EqdLinJob* jobs, int n) {
-    const char* f = eqd_tunable("EQD_LINEAR_SIMPLE");
-    if (f && f[0] == '0' && f[1] == 0) return false;
+    if (!eqd_switch_on("EQD_LINEAR_SIMPLE")) return false;
     for (int i = 0; i < n; ++i) {
         const EqdLinJob& J = jobs[i];
         if (J.nsrc != 1 || J.M != 64 || J.s[0].K != 64 || J.s[0].w_cs != 1 || J.s[0].mask || !J.s[0].W || !J.s[0].X || J.ln_g ||
@@ -838,15 +841,35 @@ static int lin_check_sources(const EqdLinJob& J) {
 // does (C fp32 7 107 -> 7 329 k_rowwave -> 7 607 k_rowres, C bf16 9 971 -> 10 537 -> 11 390, E 551 -> 552 -> 562).
 // Default: k_rowres from 3 tiles per CU, k_rowchain / k_linear below; EQD_ROWWAVE = 0 / 1 / 2 forces k_rowchain +
 // k_linear / k_rowwave / k_rowres for every eligible chain (tests, experiments).
-static int rw_mode(int rows);
-// 1 when chains over `rows` rows run on k_rowres: a wave walks a chain's jobs one after the other there, so the driver
-// appends the next layer's five projection jobs to the node-update chain (they read its result from the LDS tile)
-// instead of launching them on their own - below that size they run side by side on k_linear, which is faster
-int eqd_rows_resident(int rows) { return rows > 0 && rw_mode(rows) == 2; }
 static int rw_mode(int rows) {
     const char* f = eqd_tunable("EQD_ROWWAVE");
     if (f && f[0] >= '0' && f[0] <= '2' && f[1] == 0) return f[0] - '0';
     return (rows + 15) / 16 >= 3 * eqd_num_cus() ? 2 : 0;
+}
+// 1 when chains over `rows` rows run on k_rowres: a wave walks a chain's jobs one after the other there, so the driver
+// appends the next layer's five projection jobs to the node-update chain (they read its result from the LDS tile)
+// instead of launching them on their own - below that size they run side by side on k_linear, which is faster
+int eqd_rows_resident(int rows) { return rows > 0 && rw_mode(rows) == 2; }
+// does one of the jobs [first, last) write (as Y or pre_ln) the global rows of source S - or, with_mask, its mask rows?
+static bool chain_writes(const EqdChainJob* jobs, int first, int last, const EqdLinSrc& S, bool with_mask) {
+    for (int m = first; m < last; ++m) {
+        const float* outs[2] = {jobs[m].lin.Y, jobs[m].lin.pre_ln};
+        for (int q = 0; q < 2; ++q)
+            if (outs[q] && (outs[q] == S.X || (with_mask && outs[q] == S.mask))) return true;
+    }
+    return false;
+}
+// k_rowres / k_rowres80 keep ONE intermediate tile per (wave, tile slot): every LDS-resident source must be the tile written last
+static bool rr_single_tile(const EqdChainJob* jobs, int njobs) {
+    int cur = -1;
+    for (int i = 0; i < njobs; ++i) {
+        const EqdChainJob& C = jobs[i];
+        const int ns = C.type != 0 ? 1 : C.lin.nsrc;
+        for (int s = 0; s < ns; ++s)
+            if (C.src_local[s] >= 0 && C.src_local[s] != cur) return false;
+        if (C.out_local >= 0) cur = C.out_local;
+    }
+    return true;
 }
 static bool rw_eligible(const EqdChainJob* jobs, int njobs, int rows) {
     if (njobs <= 0 || rows <= 0 || rw_mode(rows) == 0) return false;
@@ -879,24 +902,14 @@ static bool rw_eligible(const EqdChainJob* jobs, int njobs, int rows) {
     // no global source may be data that an earlier job of the chain writes - such chains pass it on as an LDS tile
     for (int i = 0; i < njobs; ++i) {
         if (jobs[i].type != 0) continue;
-        for (int s = 0; s < jobs[i].lin.nsrc; ++s) {
-            if (jobs[i].src_local[s] >= 0) continue;
-            const EqdLinSrc& S0 = jobs[i].lin.s[s];
-            for (int m = 0; m < i; ++m) {
-                const float* outs[2] = {jobs[m].lin.Y, jobs[m].lin.pre_ln};
-                for (int q = 0; q < 2; ++q)
-                    if (outs[q] && (outs[q] == S0.X || outs[q] == S0.mask)) return false;
-            }
-        }
+        for (int s = 0; s < jobs[i].lin.nsrc; ++s)
+            if (jobs[i].src_local[s] < 0 && chain_writes(jobs, 0, i, jobs[i].lin.s[s], true)) return false;
     }
     return true;
 }
 // k_rowres80 (eqd_rowres80_inl.h): the 69-wide first layer's FORWARD jobs in bf16 mode at sizes where the row kernels keep
 // their weights in LDS.  EQD_ROWRES80=0 keeps them on the four-wave kernels (A/B runs, tests of both forms).
-int eqd_rowres80_on() {
-    const char* f = eqd_tunable("EQD_ROWRES80");
-    return !(f && f[0] == '0' && f[1] == 0);
-}
+int eqd_rowres80_on() { return eqd_switch_on("EQD_ROWRES80"); }
 static bool rw80_eligible(const EqdChainJob* jobs, int njobs, int rows) {
     if (njobs <= 0 || rows <= 0 || rw_mode(rows) != 2 || !eqd_rowres80_on()) return false;
     bool wide = false;
@@ -924,26 +937,15 @@ static bool rw80_eligible(const EqdChainJob* jobs, int njobs, int rows) {
     if (!wide) return false;      // (plain 64-wide chains: k_rowres)
     // no global source that an earlier job of the chain writes (rows are fetched ahead), one live intermediate tile
     for (int i = 0; i < njobs; ++i)
-        for (int s = 0; s < jobs[i].lin.nsrc; ++s) {
-            if (jobs[i].src_local[s] >= 0) continue;
-            for (int m = 0; m < i; ++m) {
-                const float* outs[2] = {jobs[m].lin.Y, jobs[m].lin.pre_ln};
-                for (int q = 0; q < 2; ++q)
-                    if (outs[q] && outs[q] == jobs[i].lin.s[s].X) return false;
-            }
-        }
-    int cur = -1;
-    for (int i = 0; i < njobs; ++i) {
-        const int ns = jobs[i].type != 0 ? 1 : jobs[i].lin.nsrc;
-        for (int s = 0; s < ns; ++s)
-            if (jobs[i].src_local[s] >= 0 && jobs[i].src_local[s] != cur) return false;
-        if (jobs[i].out_local >= 0) cur = jobs[i].out_local;
-    }
-    return true;
+        for (int s = 0; s < jobs[i].lin.nsrc; ++s)
+            if (jobs[i].src_local[s] < 0 && chain_writes(jobs, 0, i, jobs[i].lin.s[s], false)) return false;
+    return rr_single_tile(jobs, njobs);
 }
-static void chain_links(EqdChainArg& arg, const EqdChainJob* jobs, int njobs) {
+static void chain_links(EqdChainArg& arg) {
     // prefetch_next[i]: the next linear job n whose first step may be loaded before job i's epilogue: its first
     // source is an LDS tile, or global data that none of the jobs i .. n-1 writes
+    const EqdChainJob* jobs = arg.j;
+    const int njobs = arg.njobs;
     for (int i = 0; i < njobs; ++i) {
         arg.j[i].prefetch_next = -1;
         arg.j[i].next_lin = -1;
@@ -952,29 +954,8 @@ static void chain_links(EqdChainArg& arg, const EqdChainJob* jobs, int njobs) {
         while (n < njobs && jobs[n].type != 0) ++n;
         if (n >= njobs) continue;
         arg.j[i].next_lin = n;
-        bool ok = true;
-        if (jobs[n].src_local[0] < 0) {
-            const EqdLinSrc& S0 = jobs[n].lin.s[0];
-            for (int m = i; m < n && ok; ++m) {
-                const float* outs[2] = {jobs[m].lin.Y, jobs[m].lin.pre_ln};
-                for (int q = 0; q < 2; ++q)
-                    if (outs[q] && (outs[q] == S0.X || outs[q] == S0.mask)) ok = false;
-            }
-        }
-        if (ok) arg.j[i].prefetch_next = n;
+        if (jobs[n].src_local[0] >= 0 || !chain_writes(jobs, i, n, jobs[n].lin.s[0], true)) arg.j[i].prefetch_next = n;
     }
-}
-// k_rowres keeps ONE intermediate tile per (wave, tile slot): every LDS-resident source must be the tile written last
-static bool rr_single_tile(const EqdChainJob* jobs, int njobs) {
-    int cur = -1;
-    for (int i = 0; i < njobs; ++i) {
-        const EqdChainJob& C = jobs[i];
-        const int ns = C.type != 0 ? 1 : C.lin.nsrc;
-        for (int s = 0; s < ns; ++s)
-            if (C.src_local[s] >= 0 && C.src_local[s] != cur) return false;
-        if (C.out_local >= 0) cur = C.out_local;
-    }
-    return true;
 }
 static int rr_tiles_per_wg(int rows) {
     const char* f = eqd_tunable("EQD_ROWRES_TPS");      // tests: force the tiles per workgroup (1..16) to reach the two-slot paths
@@ -992,48 +973,36 @@ static int rr_blocks(int rows) {
     return ((rows + 15) / 16 + tps - 1) / tps;
 }
 static int rw_blocks(int rows) { return ((rows + 15) / 16 + RW_WAVES - 1) / RW_WAVES; }
-// workgroups (= LayerNorm-backward partial rows) of the launch rw_launch would make
-static int rw_launch_blocks(const EqdChainJob* jobs, int njobs, int rows) {
-    return (rw_mode(rows) == 2 && rr_single_tile(jobs, njobs)) ? rr_blocks(rows) : rw_blocks(rows);
-}
-static int launch_rowwave(const EqdChainArg& arg, int rows, bool bf, hipStream_t st) {
-    if (rw_mode(rows) == 2 && rr_single_tile(arg.j, arg.njobs)) {
-        const int tps = rr_tiles_per_wg(rows);
-        if (bf) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowres<true>), dim3(rr_blocks(rows)), dim3(64 * RR_WAVES), 0, st, arg, tps);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowres<false>), dim3(rr_blocks(rows)), dim3(64 * RR_WAVES), 0, st, arg, tps);
-        return eqd_check_launch("k_rowres");
-    }
-    if (bf) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowwave<true>), dim3(rw_blocks(rows)), dim3(64 * RW_WAVES), 0, st, arg);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowwave<false>), dim3(rw_blocks(rows)), dim3(64 * RW_WAVES), 0, st, arg);
-    return eqd_check_launch("k_rowwave");
-}
 
-// k_rowchain_res_fwd (eqd_chainres_inl.h): the forward node chain of a 64-wide layer, weights and rows resident in LDS, where
-// k_rowchain<1, false, 1> runs otherwise (one tile per workgroup, no more tiles than CUs, fp32).  EQD_CHAIN_RESIDENT=0
-// keeps k_rowchain (A/B runs, the bit comparisons of tests/test_chain_resident_*.py).  The copies move 16 bytes per lane
-// from the addresses the register loads of k_rowchain use - 4-byte aligned where a row is 261 or 69 floats long.
-static int chain_resident_on() {
-    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT");
-    return !(f && f[0] == '0' && f[1] == 0);
+// EQD_ROWCHAIN_OCC (experiments): 1 / 2 forces k_rowchain's register budget; 0: not set, -1: set to anything else
+static int rowchain_occ_forced() {
+    const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");
+    if (!(oc && oc[0])) return 0;
+    return (oc[0] == '1' || oc[0] == '2') && oc[1] == 0 ? oc[0] - '0' : -1;
 }
+// Where k_rowchain<1, *, 1> runs otherwise, the LDS-resident bodies may (each behind its switch and its match of the list):
+// one tile per workgroup, no more tiles than CUs, and no forced register budget (`occ` = rowchain_occ_forced(): set to
+// anything, it means that this experiment wants k_rowchain).
+static bool cr_rows_ok(int rows, int occ) {
+    return occ == 0 && rows > 0 && eqd_row_tiles(rows) == 1 && eqd_rowchain_blocks(rows) <= eqd_num_cus();
+}
+// k_rowchain_res_fwd (eqd_chainres_inl.h): the forward node chain of a 64-wide layer, weights and rows resident in LDS,
+// fp32.  EQD_CHAIN_RESIDENT=0 keeps k_rowchain (A/B runs, the bit comparisons of tests/test_chain_resident_*.py).  The copies
+// move 16 bytes per lane from the addresses the register loads of k_rowchain use - 4-byte aligned where a row is 261 or 69
+// floats long.
+static bool chain_resident_on() { return eqd_switch_on("EQD_CHAIN_RESIDENT"); }
 // The carrying forms (NP = 5: the next layer's five node projections behind node_mlp.4, NP = 1: the head's mlp_h_mean_ROT
 // behind the last layer's) are taken when the list continues with exactly such jobs on job 1's tile; EQD_CHAIN_RESIDENT_PROJ=0
 // keeps the two-job body and the projections' own launches.
-static int chain_resident_proj_on() {
-    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT_PROJ");
-    return chain_resident_on() && !(f && f[0] == '0' && f[1] == 0);
-}
-// may a forward chain over `rows` rows run on the resident body at all (what does not depend on the job list)?
-static bool cr_fwd_rows_ok(int rows) {
-    const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");      // (a forced register budget means: this experiment wants k_rowchain)
-    return chain_resident_on() && !(oc && oc[0]) && rows > 0 && eqd_row_tiles(rows) == 1 && eqd_rowchain_blocks(rows) <= eqd_num_cus();
-}
+static bool chain_resident_proj_on() { return chain_resident_on() && eqd_switch_on("EQD_CHAIN_RESIDENT_PROJ"); }
 // the driver asks BEFORE it builds the list: would a 64-wide layer's chain over `rows` rows carry projection jobs?
 // (rw_mode: a forced EQD_ROWWAVE hands eligible chains to k_rowwave / k_rowres before this body is asked)
-int eqd_chain_carries_proj(int rows) { return chain_resident_proj_on() && cr_fwd_rows_ok(rows) && rw_mode(rows) == 0; }
+int eqd_chain_carries_proj(int rows) {
+    return chain_resident_proj_on() && cr_rows_ok(rows, rowchain_occ_forced()) && rw_mode(rows) == 0;
+}
 // matches the list structurally and fills the kernel's compact argument; np: carried jobs (0, 1, 5)
 static bool crf_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResFwdArg& A, int& np) {
-    if (njobs < 2 || !cr_fwd_rows_ok(rows)) return false;
+    if (njobs < 2 || !chain_resident_on()) return false;
     np = njobs - 2;
     if (np != 0 && !((np == 1 || np == 5) && chain_resident_proj_on())) return false;
     const EqdChainJob &C0 = jobs[0], &C1 = jobs[1];
@@ -1081,12 +1050,8 @@ extern "C" long long eqd_chain_resident_proj_launches(void) { return g_chain_res
 // Exactly d = d0 = 69: the remainder images of the body are laid out for 5 columns beyond 64.  EQD_CHAIN_RESIDENT=0 turns
 // it off with the other resident bodies, EQD_CHAIN_RESIDENT_WIDE=0 alone.  A forced EQD_ROWWAVE keeps the list on k_rowchain
 // as well.  (Layer 0's BACKWARD chain has no resident form: it stays on k_rowchain.)
-static int chain_resident_wide_on() {
-    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT_WIDE");
-    return chain_resident_on() && !(f && f[0] == '0' && f[1] == 0);
-}
 static bool crw_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResWideArg& A) {
-    if (njobs != 2 || !chain_resident_wide_on() || !cr_fwd_rows_ok(rows) || rw_mode(rows) != 0) return false;
+    if (njobs != 2 || !chain_resident_on() || !eqd_switch_on("EQD_CHAIN_RESIDENT_WIDE") || rw_mode(rows) != 0) return false;
     const EqdChainJob &C0 = jobs[0], &C1 = jobs[1];
     const EqdLinJob &J0 = C0.lin, &J1 = C1.lin;
     if (C0.type != 0 || C1.type != 0 || J0.bf16 || J1.bf16 || J0.rows != rows || J1.rows != rows) return false;
@@ -1121,14 +1086,8 @@ extern "C" long long eqd_chain_resident_wide_launches(void) { return g_chain_res
 // argument while it checks.  eqd_node_update_bwd's list (four column blocks in another order, a residual on the last
 // block of a five-job list) stays on k_rowchain.  EQD_CHAIN_RESIDENT=0 turns off both resident bodies,
 // EQD_CHAIN_RESIDENT_BWD=0 this one alone.
-static int chain_resident_bwd_on() {
-    const char* f = eqd_tunable("EQD_CHAIN_RESIDENT_BWD");
-    return chain_resident_on() && !(f && f[0] == '0' && f[1] == 0);
-}
 static bool crb_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResBwdArg& A) {
-    if (!chain_resident_bwd_on() || (njobs != 5 && njobs != 6) || rows <= 0 || eqd_row_tiles(rows) != 1 ||
-        eqd_rowchain_blocks(rows) > eqd_num_cus())
-        return false;
+    if (!chain_resident_on() || !eqd_switch_on("EQD_CHAIN_RESIDENT_BWD") || (njobs != 5 && njobs != 6)) return false;
     const bool dh = njobs == 6;
     // a linear job of this chain: 64 outputs, fp32, transposed 64-deep weight sources, none of the optional epilogue parts
     auto plain = [&](const EqdChainJob& C, int nsrc) {
@@ -1189,6 +1148,105 @@ static bool crb_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResBwdAr
 static std::atomic<long long> g_chain_resident_bwd_launches{0};
 extern "C" long long eqd_chain_resident_bwd_launches(void) { return g_chain_resident_bwd_launches.load(); }
 
+// ---- which body runs a job list: decided here, once, for eqd_launch_rowchain and eqd_linear -----------------------------
+enum RowBody {
+    ROW_NONE,                             // (eqd_linear's question only: neither row kernel takes the jobs)
+    ROW_RES80,                            // k_rowres80
+    ROW_RES, ROW_WAVE,                    // k_rowres<bf>, k_rowwave<bf>
+    ROW_CRF0, ROW_CRF1, ROW_CRF5,         // k_rowchain_res_fwd<NP>
+    ROW_CRW,                              // k_rowchain_res_fwd_wide
+    ROW_CRB, ROW_CRB_DH,                  // k_rowchain_res_bwd<DH>
+    ROW_CHAIN                             // k_rowchain<rt, bf, occ>
+};
+struct RowPlan {
+    RowBody body;
+    int grid;                             // workgroups = rows of LayerNorm-backward partial sums the launch writes
+    int tps;                              // k_rowres80 / k_rowres: 16-row tiles per workgroup
+    bool bf;                              // one arithmetic mode per launch
+    int rt, occ;                          // k_rowchain's template form
+    union {                               // the resident bodies' packed argument
+        ChainResFwdArg f;
+        ChainResWideArg w;
+        ChainResBwdArg b;
+    } res;
+    std::atomic<long long>* count[2];     // launch counters to bump, or NULL
+};
+// The tests, in order: k_rowres80, k_rowres / k_rowwave (the row kernels: all that eqd_linear asks about, chain = false),
+// the three resident bodies, k_rowchain.
+static RowPlan row_plan(const EqdChainJob* jobs, int njobs, int rows, bool chain, bool wide_ok) {
+    RowPlan P;
+    memset(&P, 0, sizeof(P));
+    P.bf = njobs > 0 && jobs[0].lin.bf16;
+    const bool rw = rw_eligible(jobs, njobs, rows);
+    if (!rw && rw80_eligible(jobs, njobs, rows)) P.body = ROW_RES80;      // the first layer's forward chain, bf16
+    else if (rw) P.body = rw_mode(rows) == 2 && rr_single_tile(jobs, njobs) ? ROW_RES : ROW_WAVE;
+    if (P.body == ROW_WAVE) P.grid = rw_blocks(rows);
+    else if (P.body != ROW_NONE) { P.tps = rr_tiles_per_wg(rows); P.grid = rr_blocks(rows); }
+    if (P.body != ROW_NONE || !chain) return P;
+    P.grid = eqd_rowchain_blocks(rows);
+    const int occ = rowchain_occ_forced();
+    if (cr_rows_ok(rows, occ)) {
+        int np = 0;
+        if (crf_pack(jobs, njobs, rows, P.res.f, np)) {
+            P.body = np == 5 ? ROW_CRF5 : np == 1 ? ROW_CRF1 : ROW_CRF0;
+            P.count[0] = &g_chain_resident_launches;
+            if (np) P.count[1] = &g_chain_resident_proj_launches;
+            return P;
+        }
+        if (wide_ok && crw_pack(jobs, njobs, rows, P.res.w)) {
+            P.body = ROW_CRW; P.count[0] = &g_chain_resident_wide_launches;
+            return P;
+        }
+        if (crb_pack(jobs, njobs, rows, P.res.b)) {
+            P.body = njobs == 6 ? ROW_CRB_DH : ROW_CRB; P.count[0] = &g_chain_resident_bwd_launches;
+            return P;
+        }
+    }
+    P.body = ROW_CHAIN;
+    P.rt = eqd_row_tiles(rows);
+    // (the two-tile forms need more than 256 registers: one workgroup per CU at every size)
+    P.occ = P.rt == 2 ? 1 : occ > 0 ? occ : (P.grid <= eqd_num_cus() ? 1 : 2);
+    return P;
+}
+template <class... A>
+static void row_go(void (*kernel)(A...), const RowPlan& P, int threads, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(P.grid), dim3(threads), 0, st, args...);
+}
+static int row_launch(const RowPlan& P, const EqdChainArg& arg, hipStream_t st) {
+    const char* family = "k_rowchain";
+    switch (P.body) {
+    case ROW_NONE: return EQD_ERR_UNSUPPORTED;
+    case ROW_RES80: row_go(k_rowres80, P, 64 * RR_WAVES, st, arg, P.tps); family = "k_rowres"; break;
+    case ROW_RES:
+        if (P.bf) row_go(k_rowres<true>, P, 64 * RR_WAVES, st, arg, P.tps);
+        else row_go(k_rowres<false>, P, 64 * RR_WAVES, st, arg, P.tps);
+        family = "k_rowres";
+        break;
+    case ROW_WAVE:
+        if (P.bf) row_go(k_rowwave<true>, P, 64 * RW_WAVES, st, arg);
+        else row_go(k_rowwave<false>, P, 64 * RW_WAVES, st, arg);
+        family = "k_rowwave";
+        break;
+    case ROW_CRF0: row_go(k_rowchain_res_fwd<0>, P, EQD_BLOCK, st, P.res.f); break;
+    case ROW_CRF1: row_go(k_rowchain_res_fwd<1>, P, EQD_BLOCK, st, P.res.f); break;
+    case ROW_CRF5: row_go(k_rowchain_res_fwd<5>, P, EQD_BLOCK, st, P.res.f); break;
+    case ROW_CRW: row_go(k_rowchain_res_fwd_wide, P, EQD_BLOCK, st, P.res.w); break;
+    case ROW_CRB: row_go(k_rowchain_res_bwd<false>, P, EQD_BLOCK, st, P.res.b); break;
+    case ROW_CRB_DH: row_go(k_rowchain_res_bwd<true>, P, EQD_BLOCK, st, P.res.b); break;
+    case ROW_CHAIN:
+        if (P.rt == 2 && P.bf) row_go(k_rowchain<2, true, 1>, P, EQD_BLOCK, st, arg);
+        else if (P.rt == 2) row_go(k_rowchain<2, false, 1>, P, EQD_BLOCK, st, arg);
+        else if (P.bf && P.occ == 1) row_go(k_rowchain<1, true, 1>, P, EQD_BLOCK, st, arg);
+        else if (P.bf) row_go(k_rowchain<1, true, 2>, P, EQD_BLOCK, st, arg);
+        else if (P.occ == 1) row_go(k_rowchain<1, false, 1>, P, EQD_BLOCK, st, arg);
+        else row_go(k_rowchain<1, false, 2>, P, EQD_BLOCK, st, arg);
+        break;
+    }
+    for (int i = 0; i < 2; ++i)
+        if (P.count[i]) P.count[i]->fetch_add(1);
+    return eqd_check_launch(family);
+}
+
 int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_t st, int* partial_rows, bool wide_ok) {
     if (njobs <= 0 || njobs > EQD_CHAIN_MAXJOBS) {
         eqd_set_error("eqd_launch_rowchain: %d jobs (1..%d)", njobs, EQD_CHAIN_MAXJOBS);
@@ -1213,64 +1271,15 @@ int eqd_launch_rowchain(const EqdChainJob* jobs, int njobs, int rows, hipStream_
             }
     }
     arg.njobs = njobs;
-    chain_links(arg, jobs, njobs);
+    chain_links(arg);
     for (int i = 0; i < njobs; ++i)
         if (jobs[i].out_local >= LIN_LOCALS) {
             eqd_set_error("eqd_launch_rowchain: LDS tile index %d >= %d", jobs[i].out_local, LIN_LOCALS);
             return EQD_ERR_SHAPE;
         }
-    const bool bf = njobs > 0 && jobs[0].lin.bf16;     // one arithmetic mode per launch
-    if (!rw_eligible(jobs, njobs, rows) && rw80_eligible(jobs, njobs, rows)) {      // the first layer's forward chain, bf16
-        if (partial_rows) *partial_rows = rr_blocks(rows);      // (LayerNorm-backward partial sums: one row per workgroup)
-        const int tps = rr_tiles_per_wg(rows);
-        hipLaunchKernelGGL(k_rowres80, dim3(rr_blocks(rows)), dim3(64 * RR_WAVES), 0, st, arg, tps);
-        return eqd_check_launch("k_rowres");
-    }
-    if (rw_eligible(jobs, njobs, rows)) {
-        if (partial_rows) *partial_rows = rw_launch_blocks(jobs, njobs, rows);
-        return launch_rowwave(arg, rows, bf, st);
-    }
-    if (partial_rows) *partial_rows = eqd_rowchain_blocks(rows);
-    {
-        ChainResFwdArg farg;
-        int np = 0;
-        if (crf_pack(jobs, njobs, rows, farg, np)) {
-            const dim3 grid(eqd_rowchain_blocks(rows));
-            if (np == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_fwd<5>), grid, dim3(EQD_BLOCK), 0, st, farg);
-            else if (np == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_fwd<1>), grid, dim3(EQD_BLOCK), 0, st, farg);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_fwd<0>), grid, dim3(EQD_BLOCK), 0, st, farg);
-            g_chain_resident_launches.fetch_add(1);
-            if (np) g_chain_resident_proj_launches.fetch_add(1);
-            return eqd_check_launch("k_rowchain");
-        }
-        ChainResWideArg warg;
-        if (wide_ok && crw_pack(jobs, njobs, rows, warg)) {
-            hipLaunchKernelGGL(k_rowchain_res_fwd_wide, dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, warg);
-            g_chain_resident_wide_launches.fetch_add(1);
-            return eqd_check_launch("k_rowchain");
-        }
-        ChainResBwdArg barg;
-        const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");      // (a forced register budget means: this experiment wants k_rowchain)
-        if (!(oc && oc[0]) && crb_pack(jobs, njobs, rows, barg)) {
-            if (njobs == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_bwd<true>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, barg);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain_res_bwd<false>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, barg);
-            g_chain_resident_bwd_launches.fetch_add(1);
-            return eqd_check_launch("k_rowchain");
-        }
-    }
-    if (eqd_row_tiles(rows) == 2) {
-        // (the two-tile forms need more than 256 registers: one workgroup per CU at every size)
-        if (bf) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain<2, true, 1>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain<2, false, 1>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
-    } else {
-        const char* oc = eqd_tunable("EQD_ROWCHAIN_OCC");      // experiments: 1 / 2 forces a register budget
-        const bool one = oc && (oc[0] == '1' || oc[0] == '2') && oc[1] == 0 ? oc[0] == '1' : eqd_rowchain_blocks(rows) <= eqd_num_cus();
-        if (bf && one) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain<1, true, 1>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
-        else if (bf) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain<1, true, 2>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
-        else if (one) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain<1, false, 1>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rowchain<1, false, 2>), dim3(eqd_rowchain_blocks(rows)), dim3(EQD_BLOCK), 0, st, arg);
-    }
-    return eqd_check_launch("k_rowchain");
+    const RowPlan P = row_plan(jobs, njobs, rows, true, wide_ok);
+    if (partial_rows) *partial_rows = P.grid;
+    return row_launch(P, arg, st);
 }
 
 extern "C" int eqd_linear(const EqdLinJob* jobs, int njobs, void* stream) {
@@ -1286,28 +1295,19 @@ extern "C" int eqd_linear(const EqdLinJob* jobs, int njobs, void* stream) {
         memset(&carg, 0, sizeof(carg));
         bool ok = true;
         for (int i = 0; i < njobs && ok; ++i) {
-            EqdChainJob& C = carg.j[i];
-            C.lin = jobs[i];
-            for (int s = 0; s < EQD_MAX_SRC; ++s) C.src_local[s] = -1;
-            C.out_local = -1;
+            eqd_chain_job_clear(carg.j[i]);
+            carg.j[i].lin = jobs[i];
             ok = (jobs[i].Y != nullptr || jobs[i].Yb != nullptr) && jobs[i].rows == jobs[0].rows;
         }
-        if (ok && !rw_eligible(carg.j, njobs, jobs[0].rows) && rw80_eligible(carg.j, njobs, jobs[0].rows)) {
-            for (int i = 0; i < njobs; ++i)
-                if (int e = lin_check_sources(jobs[i])) return e;
-            carg.njobs = njobs;
-            const int rows80 = jobs[0].rows, tps = rr_tiles_per_wg(rows80);
-            hipLaunchKernelGGL(k_rowres80, dim3(rr_blocks(rows80)), dim3(64 * RR_WAVES), 0, st, carg, tps);
-            return eqd_check_launch("k_rowres");
-        }
-        if (ok && rw_eligible(carg.j, njobs, jobs[0].rows)) {
-            for (int i = 0; i < njobs; ++i)
-                if (int e = lin_check_sources(jobs[i])) return e;
-            carg.njobs = njobs;
-            EqdChainJob tmp[EQD_CHAIN_MAXJOBS];
-            for (int i = 0; i < njobs; ++i) tmp[i] = carg.j[i];
-            chain_links(carg, tmp, njobs);
-            return launch_rowwave(carg, jobs[0].rows, jobs[0].bf16 != 0, st);
+        if (ok) {
+            const RowPlan P = row_plan(carg.j, njobs, jobs[0].rows, false, false);
+            if (P.body != ROW_NONE) {
+                for (int i = 0; i < njobs; ++i)
+                    if (int e = lin_check_sources(jobs[i])) return e;
+                carg.njobs = njobs;
+                chain_links(carg);      // (k_rowres80 reads neither link)
+                return row_launch(P, carg, st);
+            }
         }
     }
     for (int base = 0; base < njobs; base += LIN_MAXJOBS) {
@@ -1966,8 +1966,7 @@ static int atb_next_batch(std::vector<AtbUnit>& units, size_t first, long long* 
     // that share an operand (h with six of them, dz with four: the caller lists them back to back) fetch a part's rows of
     // it into the same L2 at about the same time - and every XCD gets the same number of parts (a grid merely padded to a
     // multiple of 8 measured k_atb 443 -> 487 us in fp32 at 64 x (300, 300): three XCDs a part short per unit)
-    const char* xa = eqd_tunable("EQD_ATB_XCD_ALIGN");      // experiments: 0 = any count
-    if (!(xa && xa[0] == '0' && xa[1] == 0) && per >= 8) per = (per + 7) / 8 * 8;
+    if (eqd_switch_on("EQD_ATB_XCD_ALIGN") && per >= 8) per = (per + 7) / 8 * 8;      // experiments: 0 = any count
     per = per > ATB_MAXBLOCKS ? ATB_MAXBLOCKS : per;
     long long off = 0;
     for (int i = 0; i < n; ++i) {
@@ -2064,8 +2063,7 @@ extern "C" int eqd_atb(const EqdAtbJob* jobs, int njobs, void* partial, size_t p
 // 1 when `dh0_job` (the gradient w.r.t. h[0], a general linear job) would run on k_linear's one-tile body anyway - the form
 // that rides in k_atb: small batches (no LDS-resident-weights kernel, one row tile per workgroup)
 int eqd_atb_tail_wanted(const EqdLinJob* dh0_job, int n_atb_jobs) {
-    const char* f = eqd_tunable("EQD_ATB_TAIL");      // 0: keep the separate launches (A/B runs)
-    if (f && f[0] == '0' && f[1] == 0) return 0;
+    if (!eqd_switch_on("EQD_ATB_TAIL")) return 0;      // 0: keep the separate launches (A/B runs)
     if (!dh0_job || n_atb_jobs <= 0 || dh0_job->rows <= 0) return 0;
     if (rw_mode(dh0_job->rows) != 0 || linear_row_tiles(dh0_job->rows) != 1) return 0;
     return dh0_job->M >= 4 && dh0_job->M <= 80 && dh0_job->nsrc >= 1 && dh0_job->nsrc <= EQD_MAX_SRC && dh0_job->Y != nullptr &&
