@@ -1411,6 +1411,43 @@ extern "C" int eqd_selftest_node_chain_bwd(const EqdNodeChainBwdTest* t, int* pa
     return eqd_launch_rowchain(cj, nj, t->rows, (hipStream_t)stream, partial_rows);
 }
 
+// Test aid: the backward row chain of the 69-wide first layer (six jobs: a model of >= 2 layers, cross messages) on the
+// caller's buffers, through node_bwd_chain with the widths eqd_model_backward passes for layer 0.
+extern "C" int eqd_selftest_node_chain_bwd_wide(const EqdNodeChainBwdWideTest* t, int* partial_rows, void* stream) {
+    if (!t || !partial_rows || !t->dH_above || !t->dH || !t->Wn2 || !t->Wn1 || !t->y_act || !t->ln_g || !t->dz || !t->ln_part ||
+        !t->d_aggr_msg || !t->d_aggr_cross || !t->dh0acc) {
+        eqd_set_error("eqd_selftest_node_chain_bwd_wide: NULL argument");
+        return EQD_ERR_NULL;
+    }
+    if (t->rows <= 0) {
+        eqd_set_error("eqd_selftest_node_chain_bwd_wide: rows=%d", t->rows);
+        return EQD_ERR_SHAPE;
+    }
+    g_bf16_mode = 0;
+    const int d = 69, dh = 64;
+    EqdLinJob dhj = lin_job(t->rows, dh, t->dH, dh, t->slope, t->ln_eps);      // (dh_job of eqd_model_backward at layer 1)
+    for (int s = 0; s < 6; ++s) {
+        if (!t->dh_X[s] || !t->dh_W[s]) {
+            eqd_set_error("eqd_selftest_node_chain_bwd_wide: NULL dh source %d", s);
+            return EQD_ERR_NULL;
+        }
+        lin_src(dhj, s, t->dh_X[s], dh, dh, t->dh_W[s], 1, t->dh_wcs[s]);
+    }
+    dhj.nsrc = 6;
+    dhj.R = t->dH_above; dhj.ldr = dh; dhj.beta = 1.f - t->skip_weight_h;
+    NodeBwdChain nc;
+    nc.N = t->rows; nc.d = d; nc.da = 80; nc.d0 = d; nc.d_emb = 64; nc.ldn = 3 * d + 64; nc.dh_width = dh;
+    nc.slope = t->slope; nc.eps = t->ln_eps; nc.alpha = 1.f;      // (69 -> 64: no skip connection)
+    nc.dh = &dhj;
+    nc.dHout = t->dH;
+    nc.Wn2 = t->Wn2; nc.Wn1 = t->Wn1; nc.y_act = t->y_act; nc.ln_g = t->ln_g; nc.drop_mul = t->drop_mul;
+    nc.dz = t->dz; nc.lnp = t->ln_part; nc.d_aggr_msg = t->d_aggr_msg; nc.d_aggr_cross = t->d_aggr_cross; nc.dh0acc = t->dh0acc;
+    nc.d_h = nullptr;
+    EqdChainJob cj[8];
+    const int nj = node_bwd_chain(nc, cj);
+    return eqd_launch_rowchain(cj, nj, t->rows, (hipStream_t)stream, partial_rows);
+}
+
 // Test aid: the forward row chain of one 64-wide layer on the caller's buffers, through the list builders eqd_model_forward
 // uses (node_fwd_chain, node_pre_jobs) - so that a test can put guard rows behind a1n, y_act, h_out and the carried jobs'
 // outputs, which the model keeps inside its state arena.

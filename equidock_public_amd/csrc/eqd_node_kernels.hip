@@ -663,6 +663,8 @@ __device__ __forceinline__ void chain_lnbwd64(const JobW& W, float (*Lb)[LIN_LOC
 }
 // k_rowchain_res_bwd: the resident-weights body of the backward chain (calls chain_lnbwd64_t)
 #include "eqd_chainres_bwd_inl.h"
+// k_rowchain_res_bwd_wide: the same for the 69-wide first layer (its LayerNorm backward is chain_lnbwd<1>'s, copied there)
+#include "eqd_chainres_bwd_wide_inl.h"
 
 template <int RT>
 __device__ __forceinline__ void chain_lnbwd(const EqdChainJob& C, float (*Lb)[LIN_LOCALS][16 * LIN_S], float (*red)[256],
@@ -1049,7 +1051,7 @@ extern "C" long long eqd_chain_resident_proj_launches(void) { return g_chain_res
 // the two-job list node_fwd_chain builds for layer 0 with cross messages on (eqd_node_update_fwd at 69 x 69 builds it too).
 // Exactly d = d0 = 69: the remainder images of the body are laid out for 5 columns beyond 64.  EQD_CHAIN_RESIDENT=0 turns
 // it off with the other resident bodies, EQD_CHAIN_RESIDENT_WIDE=0 alone.  A forced EQD_ROWWAVE keeps the list on k_rowchain
-// as well.  (Layer 0's BACKWARD chain has no resident form: it stays on k_rowchain.)
+// as well.  (Layer 0's BACKWARD chain: crbw_pack below.)
 static bool crw_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResWideArg& A) {
     if (njobs != 2 || !chain_resident_on() || !eqd_switch_on("EQD_CHAIN_RESIDENT_WIDE") || rw_mode(rows) != 0) return false;
     const EqdChainJob &C0 = jobs[0], &C1 = jobs[1];
@@ -1148,6 +1150,78 @@ static bool crb_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResBwdAr
 static std::atomic<long long> g_chain_resident_bwd_launches{0};
 extern "C" long long eqd_chain_resident_bwd_launches(void) { return g_chain_resident_bwd_launches.load(); }
 
+// k_rowchain_res_bwd_wide (eqd_chainres_bwd_wide_inl.h): the backward chain of the 69-wide first layer under the same
+// conditions - the six-job list eqd_model_backward builds for layer 0 of a model with >= 2 layers and cross messages: dh of
+// layer 1 (crb_pack's dh job), alpha dH Wn2 with M = 69, LayerNorm backward over 69 features, dz (K = 69) times the Wn1
+// column blocks of 64, 69 (padded to 80) and 64 columns, the last one accumulating into itself.  Exactly d = d0 = 69, da = 80,
+// dh_width = d_emb = 64: the body's remainder images are laid out for 5 rows / columns beyond 64.  The five-job form (a
+// one-layer model) and eqd_node_update_bwd's list (no dh job, a d_h job last) stay on k_rowchain.  EQD_CHAIN_RESIDENT=0 turns
+// it off with the other resident bodies, EQD_CHAIN_RESIDENT_WIDE_BWD=0 alone; a forced EQD_ROWWAVE keeps k_rowchain too.
+static bool crbw_pack(const EqdChainJob* jobs, int njobs, int rows, ChainResBwdWideArg& AW) {
+    if (njobs != 6 || !chain_resident_on() || !eqd_switch_on("EQD_CHAIN_RESIDENT_WIDE_BWD") || rw_mode(rows) != 0) return false;
+    // a linear job of this chain: fp32, transposed K-deep weight sources, none of the optional epilogue parts
+    auto plain = [&](const EqdChainJob& C, int M, int nsrc, int K, int pad_to) {
+        const EqdLinJob& J = C.lin;
+        if (C.type != 0 || J.bf16 || J.rows != rows || J.M != M || J.nsrc != nsrc || J.act || J.bias || J.ln_g || J.ln_b ||
+            J.pre_ln || J.mul || J.pad_to != pad_to || J.Yb)
+            return false;
+        for (int s = 0; s < nsrc; ++s)
+            if (!J.s[s].W || J.s[s].mask || J.s[s].K != K || J.s[s].w_rs != 1 || J.s[s].w_cs < M) return false;
+        return true;
+    };
+    auto src = [](const EqdLinSrc& S) { return CrbSrc{S.X, S.W, S.ldx, S.w_cs}; };
+    auto out = [](const EqdLinJob& J) { return CrbOut{J.Y, J.R, J.ldy, J.ldr, J.alpha, J.beta}; };
+    memset(&AW, 0, sizeof(AW));
+    ChainResBwdArg& A = AW.c;
+    A.rows = rows; AW.M = 69; AW.pad_to = 80;
+    {
+        const EqdChainJob& C = jobs[0];
+        if (!plain(C, 64, 6, 64, 0) || C.out_local != 2 || !C.lin.Y || !C.lin.R || C.lin.ldy < 64 || C.lin.ldr < 64) return false;
+        for (int s = 0; s < 6; ++s) {
+            if (!C.lin.s[s].X || C.src_local[s] >= 0 || C.lin.s[s].ldx < 64) return false;
+            A.dh[s] = src(C.lin.s[s]);
+        }
+        A.dho = out(C.lin);
+    }
+    {
+        const EqdChainJob& C = jobs[1];
+        if (!plain(C, 69, 1, 64, 0) || C.src_local[0] != 2 || C.out_local != 0 || C.lin.Y || C.lin.R) return false;
+        A.a = src(C.lin.s[0]);
+        A.a_alpha = C.lin.alpha;
+        A.a_beta = C.lin.beta;
+    }
+    {
+        const EqdChainJob& C = jobs[2];
+        const EqdLinJob& J = C.lin;
+        if (C.type != 1 || J.bf16 || J.rows != rows || J.M != 69 || C.src_local[0] != 0 || C.out_local != 1 || !J.s[0].X ||
+            J.s[0].ldx < 69 || !J.ln_g || !J.Y || J.ldy < 69 || !C.aux || (J.mul && J.ld_mul < 69))
+            return false;
+        A.y_act = J.s[0].X; A.ld_y = J.s[0].ldx;
+        A.ln_g = J.ln_g;
+        A.mul = J.mul; A.ld_mul = J.ld_mul;
+        A.dz = J.Y; A.ld_dz = J.ldy;
+        A.aux = C.aux;
+        A.slope = J.slope; A.ln_eps = J.ln_eps;
+    }
+    const int Ms[3] = {64, 69, 64}, pads[3] = {0, 80, 0};
+    for (int j = 0; j < 3; ++j) {
+        const EqdChainJob& C = jobs[3 + j];
+        if (!plain(C, Ms[j], 1, 69, pads[j]) || C.src_local[0] != 1 || C.out_local >= 0 || !C.lin.Y ||
+            C.lin.ldy < (pads[j] ? pads[j] : Ms[j]))
+            return false;
+        // the residual: only the accumulation of dh0acc into itself (69-float rows, of which 64 columns are written)
+        if (j == 2 ? !(C.lin.R && C.lin.R == C.lin.Y && C.lin.ldr == C.lin.ldy && C.lin.ldy == 69) : C.lin.R != nullptr) return false;
+        A.x[j] = src(C.lin.s[0]);
+        A.xo[j] = out(C.lin);
+        // adjacent column blocks of ONE matrix: 64, 69 and 64 columns
+        if (j > 0 && (A.x[j].W != A.x[j - 1].W + Ms[j - 1] || A.x[j].wcs != A.x[j - 1].wcs)) return false;
+    }
+    return true;
+}
+static std::atomic<long long> g_chain_resident_wide_bwd_launches{0};
+// how many row chains ran on the wide resident backward body (none of the four counters above counts it)
+extern "C" long long eqd_chain_resident_wide_bwd_launches(void) { return g_chain_resident_wide_bwd_launches.load(); }
+
 // ---- which body runs a job list: decided here, once, for eqd_launch_rowchain and eqd_linear -----------------------------
 enum RowBody {
     ROW_NONE,                             // (eqd_linear's question only: neither row kernel takes the jobs)
@@ -1156,6 +1230,7 @@ enum RowBody {
     ROW_CRF0, ROW_CRF1, ROW_CRF5,         // k_rowchain_res_fwd<NP>
     ROW_CRW,                              // k_rowchain_res_fwd_wide
     ROW_CRB, ROW_CRB_DH,                  // k_rowchain_res_bwd<DH>
+    ROW_CRBW,                             // k_rowchain_res_bwd_wide
     ROW_CHAIN                             // k_rowchain<rt, bf, occ>
 };
 struct RowPlan {
@@ -1168,11 +1243,12 @@ struct RowPlan {
         ChainResFwdArg f;
         ChainResWideArg w;
         ChainResBwdArg b;
+        ChainResBwdWideArg bw;
     } res;
     std::atomic<long long>* count[2];     // launch counters to bump, or NULL
 };
 // The tests, in order: k_rowres80, k_rowres / k_rowwave (the row kernels: all that eqd_linear asks about, chain = false),
-// the three resident bodies, k_rowchain.
+// the four resident bodies, k_rowchain.
 static RowPlan row_plan(const EqdChainJob* jobs, int njobs, int rows, bool chain, bool wide_ok) {
     RowPlan P;
     memset(&P, 0, sizeof(P));
@@ -1199,6 +1275,10 @@ static RowPlan row_plan(const EqdChainJob* jobs, int njobs, int rows, bool chain
         }
         if (crb_pack(jobs, njobs, rows, P.res.b)) {
             P.body = njobs == 6 ? ROW_CRB_DH : ROW_CRB; P.count[0] = &g_chain_resident_bwd_launches;
+            return P;
+        }
+        if (crbw_pack(jobs, njobs, rows, P.res.bw)) {
+            P.body = ROW_CRBW; P.count[0] = &g_chain_resident_wide_bwd_launches;
             return P;
         }
     }
@@ -1233,6 +1313,7 @@ static int row_launch(const RowPlan& P, const EqdChainArg& arg, hipStream_t st) 
     case ROW_CRW: row_go(k_rowchain_res_fwd_wide, P, EQD_BLOCK, st, P.res.w); break;
     case ROW_CRB: row_go(k_rowchain_res_bwd<false>, P, EQD_BLOCK, st, P.res.b); break;
     case ROW_CRB_DH: row_go(k_rowchain_res_bwd<true>, P, EQD_BLOCK, st, P.res.b); break;
+    case ROW_CRBW: row_go(k_rowchain_res_bwd_wide, P, EQD_BLOCK, st, P.res.bw); break;
     case ROW_CHAIN:
         if (P.rt == 2 && P.bf) row_go(k_rowchain<2, true, 1>, P, EQD_BLOCK, st, arg);
         else if (P.rt == 2) row_go(k_rowchain<2, false, 1>, P, EQD_BLOCK, st, arg);

@@ -57,7 +57,7 @@ int eqd_tile_edges(void);
 int eqd_is_simulator(void);
 /* The EQD_* environment switches that select kernel forms for tests and A/B measurements (EQD_FUSE_FWD, EQD_FUSE_GATHER,
  * EQD_ATT_SPLIT, EQD_ATT_BWD_SPLIT, EQD_ATT_LB, EQD_ATT_LB_NB, EQD_ATT_DS, EQD_ATT_QDS_NB, EQD_ROWWAVE, EQD_ROW_TILES,
- * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_CHAIN_RESIDENT_BWD, EQD_CHAIN_RESIDENT_PROJ, EQD_CHAIN_RESIDENT_WIDE, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
+ * EQD_ROWRES_TPS, EQD_ROWCHAIN_OCC, EQD_CHAIN_RESIDENT, EQD_CHAIN_RESIDENT_BWD, EQD_CHAIN_RESIDENT_PROJ, EQD_CHAIN_RESIDENT_WIDE, EQD_CHAIN_RESIDENT_WIDE_BWD, EQD_ATB_WGS, EQD_ATB_XCD_ALIGN, EQD_KEYPOINT_MM, EQD_KEYPOINT_NC) are read ONCE per process, at their first use, so that the forward and the backward of a step always
  * agree on the forms they run.  A caller that changes one of them afterwards calls this to make the library forget its
  * snapshot (nothing in the reference corresponds to it). */
 void eqd_tunables_reload(void);
@@ -110,6 +110,39 @@ long long eqd_chain_resident_proj_launches(void);
  * k_rowchain for this chain alone (read once per process like the switches listed above), EQD_CHAIN_RESIDENT=0 turns off
  * every resident body. */
 long long eqd_chain_resident_wide_launches(void);
+/* Test aid: how many row chains ran on the wide resident BACKWARD body (k_rowchain_res_bwd_wide: the six-job backward node
+ * chain of the 69-wide first layer that eqd_model_backward builds for a model of >= 2 layers with cross_msgs on - dh of layer
+ * 1, alpha dH Wn2 with 69 outputs, LayerNorm backward over 69 features, dz times the Wn1 column blocks of 64, 69 (padded to
+ * 80) and 64 columns - under the conditions of the bodies above).  The four counters above never count it.
+ * EQD_CHAIN_RESIDENT_WIDE_BWD=0 keeps k_rowchain for this chain alone (read once per process like the switches listed above),
+ * EQD_CHAIN_RESIDENT=0 turns off every resident body. */
+long long eqd_chain_resident_wide_bwd_launches(void);
+/* Test aid: ONE backward node chain of the 69-wide first layer on the caller's buffers, built by the list builder
+ * eqd_model_backward uses - always the six-job form: dH = dh of layer 1 from its six sources dh_X[s] [rows][64] times
+ * transposed weights, element (m, k) at dh_W[s][m + k * dh_wcs[s]], plus (1 - skip) dH_above; then alpha = 1 dH Wn2 (Wn2
+ * [64][69]), LayerNorm backward over 69 features (y_act, drop_mul or NULL, dz: [rows][69]; ln_part [*partial_rows][256]),
+ * dz times Wn1 [69][271]: d_aggr_msg [rows][64], d_aggr_cross [rows][80] (columns 69 .. 79 written as zeros), dh0acc
+ * [rows][69] += (columns 0 .. 63).  eqd_selftest_node_chain_bwd stays the aid of the 64-wide layers. */
+typedef struct EqdNodeChainBwdWideTest {
+    int32_t rows;
+    float skip_weight_h, slope, ln_eps;
+    const float* dh_X[6];
+    const float* dh_W[6];
+    int32_t dh_wcs[6];
+    const float* dH_above;
+    float* dH;
+    const float* Wn2;
+    const float* Wn1;
+    const float* y_act;
+    const float* ln_g;
+    const float* drop_mul;
+    float* dz;
+    float* ln_part;
+    float* d_aggr_msg;
+    float* d_aggr_cross;
+    float* dh0acc;
+} EqdNodeChainBwdWideTest;
+int eqd_selftest_node_chain_bwd_wide(const EqdNodeChainBwdWideTest* t, int* partial_rows /* host */, void* stream);
 /* Test aid: ONE forward node chain of a 64-wide layer on the caller's buffers, built by the list builders eqd_model_forward
  * uses: node_mlp.0 on [h, aggr_msg, aggr_cross, h0] ([rows][64] each, h0 [rows][d0]; Wn1 [64][d0 + 192]) -> LeakyReLU
  * [* drop_mul] -> y_act -> LayerNorm -> a1n -> node_mlp.4 (Wn2 [64][64]) + skip -> h_out; form 5: then the next layer's
