@@ -144,7 +144,8 @@ EXPORTS = ('eqd_model_layer_state', 'eqd_model_lrelu_signs', 'eqd_model_head_bac
            'eqd_clash_workspace_bytes', 'eqd_clash_iterations', 'eqd_dropout_pack_edges', 'eqd_dropout_draw',
            'eqd_tunables_reload', 'eqd_node_update_fwd', 'eqd_node_update_bwd_workspace_bytes', 'eqd_node_update_bwd',
            'eqd_selftest_lane_exchanges', 'eqd_chain_resident_proj_launches', 'eqd_selftest_node_chain_fwd', 'eqd_model_node_state',
-           'eqd_chain_resident_wide_launches', 'eqd_chain_resident_wide_bwd_launches', 'eqd_selftest_node_chain_bwd_wide')
+           'eqd_chain_resident_wide_launches', 'eqd_chain_resident_wide_bwd_launches', 'eqd_selftest_node_chain_bwd_wide',
+           'eqd_edge_fwd_half_launches', 'eqd_selftest_edge_attn_fwd')
 
 
 def load_library():

@@ -342,7 +342,11 @@ __device__ __forceinline__ int att_half_of(int b) { return (b >> 3) & 1; }
 // t = the thread's index within the group (0..255).  `group_barriers`: the group shares its workgroup with other groups
 // that execute the same number of __syncthreads() (k_edge_attn_fwd: the two halves of one item) - an empty half then
 // still has to pass them.
-template <int DB, bool FAST, int NB, bool BF = false>
+// LEAN (k_edge_attn_fwd_half: 128 registers per wave): the Q fragments are re-read from the block's LDS tile in front of
+// every score product instead of living across the loop, and the prefetch of the next V tile is issued behind the score
+// product instead of in front of it, so that at most three of the four streamed tiles' registers are live at the score
+// product's peak.  Same operands, same MFMA order: the same bits.
+template <int DB, bool FAST, int NB, bool BF = false, bool LEAN = false>
 __device__ __forceinline__ void attn_fwd_body(AttnFwdSmem<DB>& sm, const EqdGraph& G, int item, int half, int t, int d,
                                               const float* __restrict__ q, const float* __restrict__ k,
                                               const float* __restrict__ v, float* __restrict__ out,
@@ -399,8 +403,10 @@ __device__ __forceinline__ void attn_fwd_body(AttnFwdSmem<DB>& sm, const EqdGrap
     __syncthreads();
     EQD_TR(2);
     KFrag<BF, KS> qf[NB];
+    if constexpr (!LEAN) {
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) kfrag_load<BF, KS>(qf[nb], Qt, 16 * nb + l15, DS, g);
+        for (int nb = 0; nb < NB; ++nb) kfrag_load<BF, KS>(qf[nb], Qt, 16 * nb + l15, DS, g);
+    }
 
     f32x4 O[DB][NB];
     float mrun[NB], lrun[NB];
@@ -421,7 +427,11 @@ __device__ __forceinline__ void attn_fwd_body(AttnFwdSmem<DB>& sm, const EqdGrap
         wave_lds_fence();
         EQD_TR(4);
         tile_load<DB, FAST>(rk, k, d, kt + 32 * EQD_WAVES, o1, lane);   // prefetch the wave's next tile
-        tile_load<DB, FAST>(rv, v, d, kt + 32 * EQD_WAVES, o1, lane);
+        if constexpr (!LEAN) tile_load<DB, FAST>(rv, v, d, kt + 32 * EQD_WAVES, o1, lane);
+        if constexpr (LEAN) {      // (behind the fence above: the loads stay inside the loop)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) kfrag_load<BF, KS>(qf[nb], Qt, 16 * nb + l15, DS, g);
+        }
         EQD_TR(5);
         f32x4 S[2][NB];
 #pragma unroll
@@ -430,6 +440,12 @@ __device__ __forceinline__ void attn_fwd_body(AttnFwdSmem<DB>& sm, const EqdGrap
             for (int nb = 0; nb < NB; ++nb) S[mb][nb] = f4zero();
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) mma_k<BF, KS, NB>(S[mb], Kw, 16 * mb + l15, DS, g, qf);
+        if constexpr (LEAN) {
+#if !defined(EQD_HOSTSIM)
+            __builtin_amdgcn_sched_barrier(0);      // (the V prefetch must not be scheduled back in front of the score product)
+#endif
+            tile_load<DB, FAST>(rv, v, d, kt + 32 * EQD_WAVES, o1, lane);
+        }
         EQD_TR(6);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {

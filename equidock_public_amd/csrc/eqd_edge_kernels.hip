@@ -27,6 +27,7 @@
 
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 
 #define WS1 45   /* row stride of the staged W1[:, 2d_in:] block (42 used + 3 zero) */
 #define WS2 68   /* row stride of staged 64x64 weights: 272 B = 17 x 16 B -> conflict-free b128 */
@@ -51,12 +52,13 @@ struct alignas(16) EdgeSmem {
     float tile[NW][TILE_FLOATS];
 };
 
-template <int NW, int TF>
+// NT: threads of the workgroup (64 NW, or 1024 when two waves share each of the NW tiles: edge_fwd_half_body)
+template <int NW, int TF, int NT = 64 * NW>
 __device__ __forceinline__ void edge_stage_weights(EdgeSmem<NW, TF>& sm, const EqdEdgeParams& P) {
     // ALL global loads of a thread (W1's feature columns, W2, Wc1, the five vectors) are issued before the first LDS
     // store (constant trip counts, fully unrolled, unpredicated): ONE L2 round trip for the whole staging - three
     // batches with their own waits were 4 200 clocks at the head of every workgroup of the backward
-    constexpr int NT = 64 * NW;
+    static_assert(1024 % NT == 0, "W2 / Wc1 are staged as 1024 float4 in whole rounds of the workgroup");
     constexpr int N1 = (64 * 11 + NT - 1) / NT, N2 = 1024 / NT;
     const int t = threadIdx.x;
     const int koff = 2 * P.d_in;
@@ -1127,6 +1129,8 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_edge_attn_fwd80(EqdGraph G, 
     }
 }
 
+#include "eqd_edge_fwd_half_inl.h"
+
 // Smallest grid with the minimal number of tile rounds: with `wg_per_cu` workgroups per CU the makespan is
 // ceil(tiles / (CUs * wg_per_cu * waves)) tile times whatever the grid, so use as few CUs as that allows
 // and leave the rest to the kernels that run concurrently on the auxiliary streams.
@@ -1170,6 +1174,10 @@ extern "C" int eqd_edge_message_fwd(const EqdGraph* g, const EqdEdgeParams* p, c
     return eqd_check_launch("k_edge_fwd");
 }
 
+static std::atomic<long long> g_edge_fwd_half_launches{0};
+// how many fused forward launches ran their edge half on half tiles (k_edge_attn_fwd_half)
+extern "C" long long eqd_edge_fwd_half_launches(void) { return g_edge_fwd_half_launches.load(); }
+
 // 1 if eqd_edge_attn_fwd will take the fused launch for this graph / width / mode (else it issues the two launches)
 int eqd_edge_attn_fused(const EqdGraph* g, const EqdEdgeParams* p, int d_att, const float* q, const float* k, const float* v) {
     if (!eqd_switch_on("EQD_FUSE_FWD")) return 0;
@@ -1203,6 +1211,18 @@ int eqd_edge_attn_fwd(const EqdGraph* g, const EqdEdgeParams* p, const float* P,
                                P, Q, x, aggr_msg, x_new, q, k, v, att_out, lse);
         return eqd_check_launch("k_edge_attn_fwd");
     }
+    // 64-wide layers: a pair of waves per tile, four waves per SIMD (eqd_edge_fwd_half_inl.h; same bits).  One tile per
+    // pair - which edge_grid gives whenever the launch is fused: n_edge <= CUs workgroups hold every tile in one round.
+    if (eqd_switch_on("EQD_EDGE_FWD_HALF") && g->n_tiles <= FWD_WAVES * n_edge) {
+        if (drop)
+            hipLaunchKernelGGL(k_edge_attn_fwd_half<true>, dim3(n_edge + g->n_att_items), dim3(64 * EDGE_HALF_WAVES), 0, st, *g, *p,
+                               n_edge, P, Q, x, aggr_msg, x_new, q, k, v, att_out, lse);
+        else
+            hipLaunchKernelGGL(k_edge_attn_fwd_half<false>, dim3(n_edge + g->n_att_items), dim3(64 * EDGE_HALF_WAVES), 0, st, *g, *p,
+                               n_edge, P, Q, x, aggr_msg, x_new, q, k, v, att_out, lse);
+        ++g_edge_fwd_half_launches;
+        return eqd_check_launch("k_edge_attn_fwd");
+    }
     if (drop)
         hipLaunchKernelGGL(k_edge_attn_fwd<true>, dim3(n_edge + g->n_att_items), dim3(64 * FWD_WAVES), 0, st, *g, *p, n_edge, P,
                            Q, x, aggr_msg, x_new, q, k, v, att_out, lse);
@@ -1210,6 +1230,17 @@ int eqd_edge_attn_fwd(const EqdGraph* g, const EqdEdgeParams* p, const float* P,
         hipLaunchKernelGGL(k_edge_attn_fwd<false>, dim3(n_edge + g->n_att_items), dim3(64 * FWD_WAVES), 0, st, *g, *p, n_edge, P,
                            Q, x, aggr_msg, x_new, q, k, v, att_out, lse);
     return eqd_check_launch("k_edge_attn_fwd");
+}
+
+// Test aid: eqd_edge_attn_fwd (not exported) on the caller's buffers, whichever launch form it selects
+extern "C" int eqd_selftest_edge_attn_fwd(const EqdGraph* g, const EqdEdgeParams* p, const float* P, const float* Q,
+                                          const float* x, float* aggr_msg, float* x_new, int d_att, const float* q,
+                                          const float* k, const float* v, float* att_out, float* lse, void* stream) {
+    if (!g || !p || !P || !Q || !x || !aggr_msg || !x_new || !q || !k || !v || !att_out || !lse) {
+        eqd_set_error("eqd_selftest_edge_attn_fwd: NULL argument");
+        return EQD_ERR_NULL;
+    }
+    return eqd_edge_attn_fwd(g, p, P, Q, x, aggr_msg, x_new, d_att, q, k, v, att_out, lse, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -452,6 +452,20 @@ typedef struct EqdEdgeParams {
 /* P = h W1[:, :d_in]^T, Q = h W1[:, d_in:2 d_in]^T + b1 are node-level inputs ([n_nodes][64]). */
 int eqd_edge_message_fwd(const EqdGraph* g, const EqdEdgeParams* p, const float* P, const float* Q,
                          const float* x, float* aggr_msg, float* x_new, void* stream);
+/* Test aid: how many fused edge-message + attention forward launches (small batches: both halves resident on the chip at
+ * once) ran their edge half on HALF tiles (k_edge_attn_fwd_half, csrc/eqd_edge_fwd_half_inl.h: a pair of waves per 32-edge
+ * tile, 16 edges each, 16-wave workgroups, four waves per SIMD; bit-identical to k_edge_attn_fwd).  Taken for the 64-wide
+ * layers in fp32 (+ 7 per forward of an 8-layer model); the 69-wide first layer (k_edge_attn_fwd80), bf16 and every batch
+ * that is not fused never count.  EQD_EDGE_FWD_HALF=0 keeps k_edge_attn_fwd (read once per process like the other
+ * switches; eqd_tunables_reload). */
+long long eqd_edge_fwd_half_launches(void);
+/* Test aid: the edge-message forward and the cross-attention forward of ONE layer on the caller's buffers through the
+ * selection eqd_model_forward uses (one fused launch when both fit the chip at once - on whole or half tiles -, the two
+ * separate launches otherwise): aggr_msg [n_nodes][64], x_new [n_nodes][3], att_out [n_nodes][d_att], lse [n_nodes];
+ * q, k, v [n_nodes][d_att]. */
+int eqd_selftest_edge_attn_fwd(const EqdGraph* g, const EqdEdgeParams* p, const float* P, const float* Q, const float* x,
+                               float* aggr_msg, float* x_new, int d_att, const float* q, const float* k, const float* v,
+                               float* att_out, float* lse, void* stream);
 /* Backward: recomputes the tile forward; outputs dP, dQ [n_nodes][64], dx [n_nodes][3]
  * (= (1-eta) d_xnew + geometric terms), and the parameter gradients (accumulated).  The weight-gradient
  * GEMMs (dW2, dWc1, dW1[:, 2d:]) are fused into the kernel: per-edge operands never reach HBM. */
