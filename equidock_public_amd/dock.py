@@ -34,6 +34,9 @@ QUALITY_COLS = 16          # EQD_DOCK_QUALITY_COLS
 DOCK_EMD_ABI = 1
 EMD_MAX_NODES = 2048       # EQD_DOCK_EMD_MAX_NODES
 EMD_RESIDENT_CELLS = 8192  # EQD_DOCK_EMD_RESIDENT_CELLS
+DOCK_SASA_ABI = 1
+SASA_COLS = 12             # EQD_DOCK_SASA_COLS
+SASA_MAX_POINTS = 1024     # EQD_DOCK_SASA_MAX_POINTS
 
 _dock = None
 _dock_is_sim = False
@@ -80,6 +83,14 @@ def _declare(lib):
     lib.eqd_dock_quality_eval.restype = C.c_int
     lib.eqd_dock_quality_eval.argtypes = ([C.c_int] + [C.c_void_p] * 12 + [C.c_double] * 3 + [C.c_int, C.c_void_p, C.c_void_p,
                                                                                              C.c_size_t, C.c_void_p])
+    lib.eqd_dock_sasa_abi.restype = C.c_int
+    lib.eqd_dock_sasa_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_sasa_workspace_bytes.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int]
+    lib.eqd_dock_sasa_init.restype = C.c_int
+    lib.eqd_dock_sasa_init.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_sasa_eval.restype = C.c_int
+    lib.eqd_dock_sasa_eval.argtypes = ([C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 6 +
+                                       [C.c_size_t, C.c_void_p])
     lib.eqd_dock_emd_abi.restype = C.c_int
     lib.eqd_dock_emd_workspace_bytes.restype = C.c_size_t
     lib.eqd_dock_emd_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_int]
@@ -104,6 +115,8 @@ def _bind(path):
         raise _lib.EquidockHipError(f"{path}: dock quality ABI {lib.eqd_dock_quality_abi()} != {DOCK_QUALITY_ABI}")
     if lib.eqd_dock_emd_abi() != DOCK_EMD_ABI:
         raise _lib.EquidockHipError(f"{path}: dock EMD ABI {lib.eqd_dock_emd_abi()} != {DOCK_EMD_ABI}")
+    if lib.eqd_dock_sasa_abi() != DOCK_SASA_ABI:
+        raise _lib.EquidockHipError(f"{path}: dock SASA ABI {lib.eqd_dock_sasa_abi()} != {DOCK_SASA_ABI}")
     _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
     return lib
 
@@ -431,14 +444,9 @@ def _is_hydrogen(name, element):
     return name.strip().lstrip('0123456789')[:1].upper() in ('H', 'D')
 
 
-def atom_table(x):
-    """The heavy atoms of a PDB path or of a list of featurize.Residue, in file (list) order:
-    (coordinates [n, 3] float32, index [n] int64 of those rows among ALL ATOM rows - the rows of inference.read_pdb_atoms /
-    featurize.atoms_ragged -, residue offsets [n_res + 1] int32 into the n rows, backbone mask [n] uint8 (atoms named N,
-    CA, C or O), atom names [n]).  A residue is a maximal run of consecutive ATOM rows that share chain, residue number,
-    insertion code and residue name - file order, not the sorted grouping of featurize.read_pdb_residues; a run whose
-    atoms are all hydrogens has no row and no residue."""
-    rows = []              # (residue key, name, element, xyz) of every ATOM row
+def _atom_rows(x):
+    """(residue key, name, element, xyz) of every ATOM row of a PDB path or of a list of featurize.Residue"""
+    rows = []
     if isinstance(x, (str, os.PathLike)):
         with open(x) as f:
             for line in f:
@@ -452,6 +460,17 @@ def atom_table(x):
             els = r.elements if len(r.elements) == len(r.atom_names) else [''] * len(r.atom_names)
             for name, el, xyz in zip(r.atom_names, els, r.coords):
                 rows.append((key, name.strip(), el, xyz))
+    return rows
+
+
+def atom_table(x):
+    """The heavy atoms of a PDB path or of a list of featurize.Residue, in file (list) order:
+    (coordinates [n, 3] float32, index [n] int64 of those rows among ALL ATOM rows - the rows of inference.read_pdb_atoms /
+    featurize.atoms_ragged -, residue offsets [n_res + 1] int32 into the n rows, backbone mask [n] uint8 (atoms named N,
+    CA, C or O), atom names [n]).  A residue is a maximal run of consecutive ATOM rows that share chain, residue number,
+    insertion code and residue name - file order, not the sorted grouping of featurize.read_pdb_residues; a run whose
+    atoms are all hydrogens has no row and no residue."""
+    rows = _atom_rows(x)
     index, names, coords, off, prev = [], [], [], [0], None
     for k, (key, name, el, xyz) in enumerate(rows):
         new_run = key != prev
@@ -585,6 +604,171 @@ def pose_quality_batch(lig_pred_list, lig_true_list, rec_true_list, lig_res_offs
               clash_cutoff=clash_cutoff)
     res = {k: out[:, i] for i, k in enumerate(QUALITY_KEYS)}
     res.update(quality=out, plan=plan)
+    return res
+
+
+# ---- batched solvent-accessible surface: SASA, buried surface area, buried atoms and residues ------------------------
+SURFACE_KEYS = ('sasa_ligand', 'sasa_receptor', 'sasa_complex', 'bsa', 'bsa_ligand', 'bsa_receptor', 'buried_atoms_ligand',
+                'buried_atoms_receptor', 'buried_residues_ligand', 'buried_residues_receptor', 'points_alone',
+                'points_complex')
+ATOM_RADII = {'C': 1.70, 'N': 1.55, 'O': 1.52, 'S': 1.80}
+DEFAULT_RADIUS = 1.80
+
+
+def surface_all_partners():
+    """EQD_DOCK_SASA_ALL_PARTNERS=1 sends every atom of the surface pass down the path that walks all atoms of its complex
+    instead of its neighbour list (the path of an atom whose list overflows); same results, bit for bit."""
+    return os.environ.get('EQD_DOCK_SASA_ALL_PARTNERS', '0') == '1'
+
+
+def sphere_points(n):
+    """n unit vectors [n, 3] float64 on a golden-section spiral: z_k = 1 - (2k + 1) / n, rho = sqrt(1 - z_k^2),
+    phi = k * pi * (3 - sqrt(5)), rows (rho cos phi, rho sin phi, z_k)."""
+    n = int(n)
+    if n < 1 or n > SASA_MAX_POINTS:
+        raise ValueError(f"sphere_points: n = {n} (need 1..{SASA_MAX_POINTS})")
+    k = np.arange(n, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / n
+    rho = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.ascontiguousarray(np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=1))
+
+
+def atom_radii(x):
+    """float32 radii [n] of the rows of atom_table(x): C 1.70, N 1.55, O 1.52, S 1.80, anything else 1.80, by the element
+    column when it is present, otherwise by the first letter of the atom name after leading digits."""
+    out = []
+    for _, name, el, _ in _atom_rows(x):
+        if _is_hydrogen(name, el):
+            continue
+        sym = el.strip().upper() or name.strip().lstrip('0123456789')[:1].upper()
+        out.append(ATOM_RADII.get(sym, DEFAULT_RADIUS))
+    return np.asarray(out, dtype=np.float32)
+
+
+def _radii_table(r, what):
+    r = np.ascontiguousarray(np.asarray(r, dtype=np.float32).reshape(-1))
+    if not (np.isfinite(r).all() and (r > 0).all()):
+        raise ValueError(f"{what}: radii must be finite and > 0")
+    return r
+
+
+class SurfacePlan:
+    """Workspace and tables of eqd_dock_sasa_eval for one batch of complexes: the sphere table, the per-complex residue
+    offsets (local: [n_res + 1] into the complex's own rows) and the radii ([n_atoms] float32, finite and > 0) go up in ONE
+    copy, the workspace is created and initialised once (init copies the item table and waits for that copy); `eval` then
+    only enqueues launches - it can be captured into a hipGraph."""
+
+    def __init__(self, lig_res_offsets, rec_res_offsets, lig_radii, rec_radii, dev, n_points=96):
+        lib = load_dock_library()
+        n = len(lig_res_offsets)
+        if n == 0 or not (n == len(rec_res_offsets) == len(lig_radii) == len(rec_radii)):
+            raise ValueError(f"{n} ligand residue tables for {len(rec_res_offsets)} receptor residue tables, "
+                             f"{len(lig_radii)} ligand and {len(rec_radii)} receptor radius tables")
+        lr = [_radii_table(r, f'complex {c}: ligand') for c, r in enumerate(lig_radii)]
+        rr = [_radii_table(r, f'complex {c}: receptor') for c, r in enumerate(rec_radii)]
+        lro = [_residue_table(o, len(r), f'complex {c}: ligand') for c, (o, r) in enumerate(zip(lig_res_offsets, lr))]
+        rro = [_residue_table(o, len(r), f'complex {c}: receptor') for c, (o, r) in enumerate(zip(rec_res_offsets, rr))]
+        self.n, self.dev, self.n_points = n, torch.device(dev), int(n_points)
+        _require_device(torch.empty(0, device=self.dev), 'surface inputs')
+        sphere = sphere_points(self.n_points)
+        self.lig_atom_off, self.rec_atom_off = _offsets([len(r) for r in lr]), _offsets([len(r) for r in rr])
+        self.lig_res_off, self.rec_res_off = _offsets([len(o) - 1 for o in lro]), _offsets([len(o) - 1 for o in rro])
+        self._off = tuple(a.ctypes.data_as(C.c_void_p) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off,
+                                                                  self.rec_res_off))
+        Al, Ar, Rl, Rr = (int(a[-1]) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off, self.rec_res_off))
+        self.sizes = (Al, Ar, Rl, Rr)
+        # one staging buffer, one upload: fp64 sphere table | int32 first rows of the ligand, of the receptor residues |
+        # fp32 radii of the ligand, of the receptor atoms
+        nb_s, nb_f = 24 * self.n_points, 4 * (Rl + Rr + 2)
+        host = _staging(nb_s + nb_f + 4 * (Al + Ar), torch.uint8, self.dev)
+        h = host.numpy()
+        h[:nb_s].view(np.float64)[:] = sphere.reshape(-1)
+        first = h[nb_s:nb_s + nb_f].view(np.int32)
+        first[:Rl + 1] = np.concatenate([o[:-1] + int(a) for o, a in zip(lro, self.lig_atom_off)] + [[Al]])
+        first[Rl + 1:] = np.concatenate([o[:-1] + int(a) for o, a in zip(rro, self.rec_atom_off)] + [[Ar]])
+        h[nb_s + nb_f:].view(np.float32)[:] = np.concatenate(lr + rr)
+        self.tables = host.to(self.dev, non_blocking=True)
+        self.sphere = self.tables[:nb_s].view(torch.float64).view(self.n_points, 3)
+        ints = self.tables[nb_s:nb_s + nb_f].view(torch.int32)
+        self.lig_first, self.rec_first = ints[:Rl + 1], ints[Rl + 1:]
+        rad = self.tables[nb_s + nb_f:].view(torch.float32)
+        self.lig_radii, self.rec_radii = rad[:Al], rad[Al:]
+        self.atom_pairs = int(sum((a + b) * (a + b - 1) for a, b in zip(np.diff(self.lig_atom_off).astype(np.int64),
+                                                                         np.diff(self.rec_atom_off).astype(np.int64))))
+        self.wsb = lib.eqd_dock_sasa_workspace_bytes(n, *self._off, self.n_points)
+        if self.wsb == 0:
+            check(2)
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        with _lib.device_guard(self.dev):
+            check(lib.eqd_dock_sasa_init(n, *self._off, self.n_points, _lib.ptr(self.ws), C.c_size_t(self.wsb),
+                                         _stream(self.dev)))
+
+    def outputs(self):
+        """Freshly allocated output buffers of one eval: (points [A_l + A_r][2] int32, residue areas [R_l + R_r][2] fp64,
+        rows [C][12] fp64); the ligand's rows come first in the first two."""
+        Al, Ar, Rl, Rr = self.sizes
+        return (torch.empty(Al + Ar, 2, dtype=torch.int32, device=self.dev),
+                torch.empty(Rl + Rr, 2, dtype=torch.float64, device=self.dev),
+                torch.empty(self.n, SASA_COLS, dtype=torch.float64, device=self.dev))
+
+    def eval(self, lig, rec, points, res_area, rows, probe=1.4, all_partners=None):
+        """Enqueue the surface pass on the current stream: lig [A_l][3], rec [A_r][3] fp32 contiguous, the buffers of
+        `outputs()`.  No synchronisation, no allocation, no copy."""
+        Al, Ar, Rl, Rr = self.sizes
+        all_partners = surface_all_partners() if all_partners is None else bool(all_partners)
+        with _lib.device_guard(self.dev):
+            check(_dock.eqd_dock_sasa_eval(self.n, *self._off, _lib.ptr(lig), _lib.ptr(rec), _lib.ptr(self.lig_radii),
+                                           _lib.ptr(self.rec_radii), _lib.ptr(self.lig_first), _lib.ptr(self.rec_first),
+                                           _lib.ptr(self.sphere), self.n_points, C.c_double(float(probe)),
+                                           int(all_partners), _lib.ptr(points[:Al]), _lib.ptr(points[Al:]),
+                                           _lib.ptr(res_area[:Rl]), _lib.ptr(res_area[Rl:]), _lib.ptr(rows),
+                                           _lib.ptr(self.ws), C.c_size_t(self.wsb), _stream(self.dev)))
+        return rows
+
+
+def surface_area_batch(lig_list, rec_list, lig_radii=None, rec_radii=None, lig_res_offsets=None, rec_res_offsets=None,
+                       probe=1.4, n_points=96, plan=None):
+    """Solvent-accessible surface of C complexes in one device pass over every heavy atom (eqd_dock_sasa_*; the
+    definitions are in include/equidock_dock.h): Shrake-Rupley with `n_points` golden-spiral points per atom and a probe
+    of `probe` Angstrom.  It needs no native structure.  The lists hold device tensors [n_c, 3] of heavy atoms; per complex
+    (host arrays, as `atom_radii` / `atom_table` return them) the radii [n_c] (finite, > 0) and the residue offsets
+    [n_res + 1] into its own rows of each side - or a `plan` (SurfacePlan) that already holds them, so that repeated
+    evaluation of the same complexes reuses tables and workspace.  fp64 on the device from the fp32 rows; a complex's
+    results are bit-identical alone, in any batch and from run to run.
+
+    Returns a dict of device tensors: SURFACE_KEYS (float64 [C]: sasa_ligand, sasa_receptor, sasa_complex, bsa, bsa_ligand,
+    bsa_receptor, buried_atoms_ligand / _receptor, buried_residues_ligand / _receptor, points_alone, points_complex),
+    `rows`, the raw [C][12] buffer, `lig_points` / `rec_points` (int32 [A][2]: exposed points alone, in complex),
+    `lig_res_area` / `rec_res_area` (float64 [R][2]) and `plan`.  One upload of the small tables (when no plan is given),
+    one launch sequence; apart from the item-table copy of the workspace's init the call does not synchronise and
+    downloads nothing."""
+    ligs, recs = list(lig_list), list(rec_list)
+    n = len(ligs)
+    if n != len(recs):
+        raise ValueError(f"{n} ligands for {len(recs)} receptors")
+    if n == 0:
+        raise ValueError("surface_area_batch: no complexes")
+    ligs, recs = _meter_rows(ligs, 'ligand'), _meter_rows(recs, 'receptor')
+    dev = ligs[0].device
+    if plan is None:
+        if lig_radii is None or rec_radii is None or lig_res_offsets is None or rec_res_offsets is None:
+            raise ValueError("surface_area_batch: radii and residue offsets of both sides (or a plan) are needed")
+        plan = SurfacePlan(list(lig_res_offsets), list(rec_res_offsets), list(lig_radii), list(rec_radii), dev,
+                           n_points=n_points)
+    if plan.n != n:
+        raise ValueError(f"the plan holds {plan.n} complexes, the lists {n}")
+    for c in range(n):
+        nl, nr = int(plan.lig_atom_off[c + 1] - plan.lig_atom_off[c]), int(plan.rec_atom_off[c + 1] - plan.rec_atom_off[c])
+        if ligs[c].shape[0] != nl or recs[c].shape[0] != nr:
+            raise ValueError(f"complex {c}: {ligs[c].shape[0]} ligand and {recs[c].shape[0]} receptor rows for tables of "
+                             f"{nl} and {nr} atoms")
+    points, res_area, rows = plan.outputs()
+    plan.eval(torch.cat(ligs, 0), torch.cat(recs, 0), points, res_area, rows, probe=probe)
+    Al, Rl = plan.sizes[0], plan.sizes[2]
+    res = {k: rows[:, i] for i, k in enumerate(SURFACE_KEYS)}
+    res.update(rows=rows, lig_points=points[:Al], rec_points=points[Al:], lig_res_area=res_area[:Rl],
+               rec_res_area=res_area[Rl:], plan=plan)
     return res
 
 
@@ -812,6 +996,42 @@ def _chunk_quality(chunk, truths, first, final_lig, rec_atoms, cuts, dev):
     return q['quality'].cpu().numpy()
 
 
+def _chunk_surface(chunk, truths, first, final_lig, rec_atoms, probe, n_points, dev):
+    """The surface stage of dock_complexes for one chunk: the heavy-atom rows of the final ligands and of the receptors
+    taken on the device by an index built on the host, one surface_area_batch - with `truths` the native ligands ride in
+    the SAME batch as C more complexes against the same receptors -, ONE download of the [C or 2 C][12] rows."""
+    lig_t, rec_t = [], []
+    for k, (lig_in, rec_in) in enumerate(chunk):
+        lig_t.append(atom_table(lig_in) + (atom_radii(lig_in),))
+        rec_t.append(atom_table(rec_in) + (atom_radii(rec_in),))
+        if len(lig_t[-1][4]) == 0 or len(rec_t[-1][4]) == 0:
+            raise ValueError(f"complex {first + k}: a side without a heavy atom")
+    gts = []
+    for k, gt in enumerate(truths or []):
+        gts.append(atom_table(gt) + (atom_radii(gt),))
+        if len(gts[-1][4]) == 0:
+            raise ValueError(f"complex {first + k}: a ground-truth ligand without a heavy atom")
+    n = len(chunk)
+    idx = [t[1] for t in lig_t + rec_t]
+    hidx = _staging(sum(len(a) for a in idx), torch.int64, dev)
+    hidx.numpy()[:] = np.concatenate(idx)
+    didx = hidx.to(dev, non_blocking=True)
+    ioff = np.concatenate([[0], np.cumsum([len(a) for a in idx])])
+    ligs = [final_lig[k].index_select(0, didx[ioff[k]:ioff[k + 1]]) for k in range(n)]
+    recs = [rec_atoms[k].index_select(0, didx[ioff[n + k]:ioff[n + k + 1]]) for k in range(n)]
+    if gts:
+        hgt = _staging(3 * sum(len(t[0]) for t in gts), torch.float32, dev)
+        hgt.numpy()[:] = np.concatenate([t[0] for t in gts], 0).reshape(-1)
+        dgt = hgt.to(dev, non_blocking=True).view(-1, 3)
+        goff = np.concatenate([[0], np.cumsum([len(t[0]) for t in gts])])
+        ligs += [dgt[goff[k]:goff[k + 1]] for k in range(n)]
+        recs += recs
+    s = surface_area_batch(ligs, recs, [t[5] for t in lig_t + gts], [t[5] for t in rec_t] * (2 if gts else 1),
+                           [t[2] for t in lig_t + gts], [t[2] for t in rec_t] * (2 if gts else 1), probe=probe,
+                           n_points=n_points)
+    return s['rows'].cpu().numpy()
+
+
 def _sync(dev):
     if dev.type == 'cuda':
         torch.cuda.synchronize(dev)
@@ -841,7 +1061,7 @@ def _chunk_graphs(chunk, cutoff, max_neighbor, dev):
 def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=None, device=None, cutoff=30.0,
                    max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50,
                    batched_graphs=True, ground_truth=None, interface_cutoff=8.0, quality=False,
-                   quality_cutoffs=(5.0, 10.0, 3.0)):
+                   quality_cutoffs=(5.0, 10.0, 3.0), surface=False, surface_probe=1.4, surface_points=96):
     """Dock a list of (ligand, receptor) complexes, each side a PDB path or a list of featurize.Residue (the ligand's
     file / residues in their input pose, the receptor's in the bound pose - the reference's `*_l_b.pdb` and
     `*_r_b_COMPLEX.pdb`).  Per chunk of `max_complexes_per_batch` complexes (all at once by default): graphs on the
@@ -865,7 +1085,14 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
     `dockq`, `fnat`, `fnonnat`, `irmsd_backbone`, `lrmsd` (floats, NaN where undefined), `native_contacts`,
     `model_contacts` and `clashes` (ints); batch_seconds gains 'quality'.  `quality_cutoffs`: contact, interface and clash
     cutoff.  A ligand whose heavy-atom names differ from its ground truth's raises ValueError naming the complex.
-    quality=False changes nothing."""
+    quality=False changes nothing.
+
+    `surface` (needs no ground truth): each chunk ends with one surface_area_batch over EVERY heavy atom of its final
+    ligands and receptors (taken on the device; radii by atom_radii, probe `surface_probe`, `surface_points` sphere points)
+    and one more download, and the results gain `sasa_ligand`, `sasa_receptor`, `sasa_complex`, `bsa` (floats, square
+    Angstrom), `buried_atoms_ligand`, `buried_atoms_receptor`, `buried_residues_ligand` and `buried_residues_receptor`
+    (ints); batch_seconds gains 'surface'.  With `ground_truth` the native ligands go into the same batch as C more
+    complexes and the results gain `bsa_native`.  surface=False changes nothing."""
     complexes = list(complexes)
     if quality and ground_truth is None:
         raise ValueError("quality=True needs ground_truth")
@@ -916,7 +1143,7 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
             t4 = time.perf_counter()
             times = {'graphs': t1 - t0, 'model': t2 - t1, 'rigid': t3 - t2, 'clashes': t4 - t3, 'total': t4 - t0,
                      'n_complexes': len(chunk)}
-            rows = qrows = None
+            rows = qrows = srows = None
             if ground_truth is not None:
                 final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
                 rows = _chunk_metrics(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, interface_cutoff, dev)
@@ -926,6 +1153,13 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                     qrows = _chunk_quality(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, quality_cutoffs, dev)
                     t6 = time.perf_counter()       # (the download has synchronised)
                     times.update(quality=t6 - t5, total=t6 - t0)
+            if surface:
+                final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
+                ts = time.perf_counter()           # (every earlier stage has synchronised)
+                srows = _chunk_surface(chunk, None if ground_truth is None else ground_truth[b0:b0 + len(chunk)], b0, final,
+                                       rec_atoms, surface_probe, surface_points, dev)
+                te = time.perf_counter()           # (the download has synchronised)
+                times.update(surface=te - ts, total=te - t0)
             for i in range(len(chunk)):
                 results.append({'rotation': rots[i].detach().cpu().numpy(), 'translation': trs[i].detach().cpu().numpy().reshape(3),
                                 'ligand_atoms_docked': docked[i],
@@ -942,6 +1176,13 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                     results[-1].update(dockq=float(q[0]), fnat=float(q[1]), fnonnat=float(q[2]), irmsd_backbone=float(q[3]),
                                        lrmsd=float(q[4]), native_contacts=int(q[5]), model_contacts=int(q[6]),
                                        clashes=int(q[11]))
+                if srows is not None:
+                    s = srows[i]
+                    results[-1].update(sasa_ligand=float(s[0]), sasa_receptor=float(s[1]), sasa_complex=float(s[2]),
+                                       bsa=float(s[3]), buried_atoms_ligand=int(s[6]), buried_atoms_receptor=int(s[7]),
+                                       buried_residues_ligand=int(s[8]), buried_residues_receptor=int(s[9]))
+                    if ground_truth is not None:
+                        results[-1].update(bsa_native=float(srows[len(chunk) + i, 3]))
     finally:
         net.train(was_training)
     return results
@@ -974,6 +1215,10 @@ def main(argv=None):
     p.add_argument('--dockq', action='store_true',
                    help='fnat, LRMSD, backbone iRMSD, DockQ and the clashes of every docked pose from one batched device pass '
                         'per batch over every heavy atom (needs every <name>_l_b_COMPLEX.pdb)')
+    p.add_argument('--surface', action='store_true',
+                   help='solvent-accessible surface of every docked pose from one batched device pass per batch over every '
+                        'heavy atom: buried surface area and buried residues (needs no ground truth; when every '
+                        '<name>_l_b_COMPLEX.pdb is present, the native BSA as well)')
     a = p.parse_args(argv)
     try:
         names = sorted(os.path.basename(f)[:-len('_l_b.pdb')] for f in glob.glob(os.path.join(a.input_dir, '*_l_b.pdb')))
@@ -992,6 +1237,9 @@ def main(argv=None):
                 if not os.path.isfile(gt):
                     raise FileNotFoundError(f"{gt} is missing ({'--device-metrics' if a.device_metrics else '--dockq'} "
                                             "needs the ground-truth ligand of every complex)")
+        if a.surface and truths is None:
+            gts = [os.path.join(a.gt_dir, nm + '_l_b_COMPLEX.pdb') for nm in names]
+            truths = gts if all(os.path.isfile(g) for g in gts) else None
         os.makedirs(a.out_dir, exist_ok=True)
         dev = torch.device(a.device)
         net = load_checkpoint(a.checkpoint, dev)
@@ -1000,9 +1248,9 @@ def main(argv=None):
         res = dock_complexes(net, complexes, remove_clashes=a.remove_clashes, max_complexes_per_batch=a.batch or None,
                              device=dev, cutoff=float(ca.get('graph_cutoff', 30.0)),
                              max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it,
-                             batched_graphs=not a.no_batched_graphs, ground_truth=truths, quality=a.dockq)
+                             batched_graphs=not a.no_batched_graphs, ground_truth=truths, quality=a.dockq, surface=a.surface)
         suffix = '_EQUIDOCK_NO_CLASHES.pdb' if a.remove_clashes else '_EQUIDOCK.pdb'
-        crmsd, irmsd, dockq = [], [], []
+        crmsd, irmsd, dockq, bsa, bsa_native = [], [], [], [], []
         for nm, (lig_path, rec_path), r in zip(names, complexes, res):
             out = os.path.join(a.out_dir, nm + '_l_b' + suffix)
             INF.write_pdb_coordinates(lig_path, r['ligand_atoms'], out)
@@ -1025,6 +1273,13 @@ def main(argv=None):
                 dockq.append(r['dockq'])
                 line += (f"  DockQ {r['dockq']:.3f}  fnat {r['fnat']:.3f}  LRMSD {r['lrmsd']:.3f}  "
                          f"iRMSD(bb) {r['irmsd_backbone']:.3f}  clashes {r['clashes']}")
+            if a.surface:
+                bsa.append(r['bsa'])
+                line += (f"  BSA {r['bsa']:.1f}  buried residues {r['buried_residues_ligand']} / "
+                         f"{r['buried_residues_receptor']}")
+                if 'bsa_native' in r:
+                    bsa_native.append(r['bsa_native'])
+                    line += f"  native BSA {r['bsa_native']:.1f}"
             print(line, flush=True)
         wall = time.perf_counter() - t0
         print(f"Mean runtime: {wall / len(res):.4f} s per complex ({len(res)} complexes, {wall:.3f} s)")
@@ -1038,6 +1293,10 @@ def main(argv=None):
             print("CAPRI classes (DockQ): incorrect %d  acceptable %d  medium %d  high %d" %
                   (int((ok < 0.23).sum()), int(((ok >= 0.23) & (ok < 0.49)).sum()), int(((ok >= 0.49) & (ok < 0.80)).sum()),
                    int((ok >= 0.80).sum())) + ("  undefined %d" % (dq.size - ok.size) if ok.size < dq.size else ""))
+        if bsa:
+            print("BSA median/mean/std: %.1f / %.1f / %.1f" % _stats(bsa))
+        if bsa_native:
+            print("native BSA median/mean/std: %.1f / %.1f / %.1f" % _stats(bsa_native))
     except Exception as e:          # noqa: BLE001 - a command-line tool: report and exit non-zero
         print(f"error: {type(e).__name__}: {e}", file=sys.stderr)
         return 1

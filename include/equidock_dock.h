@@ -202,6 +202,75 @@ EQD_DOCK_API int eqd_dock_quality_eval(int n_complex, const int32_t* lig_atom_of
                                        void* workspace, size_t ws_bytes, void* stream);
 
 /*
+ * Batched solvent-accessible surface: Shrake-Rupley over EVERY heavy atom of C complexes in one device pass - the SASA of
+ * each partner and of the complex, the buried surface area (BSA) and the atoms and residues whose accessibility drops on
+ * binding.  It needs no native structure.  fp64 arithmetic from the fp32 inputs, without contraction, exactly as written
+ * below; a complex's results are bit-identical alone, in any batch, at any position and from run to run.
+ *
+ * Layout: the complexes are stored one after another (offsets and residue tables as for the quality pass above).
+ *   lig [A_l][3], rec [A_r][3] fp32 heavy-atom rows; lig_radius [A_l], rec_radius [A_r] fp32 atomic radii (finite, > 0: the
+ *     caller's to check, the library cannot read them)
+ *   lig_atom_off / rec_atom_off / lig_res_off / rec_res_off [C + 1]  HOST int32, as for eqd_dock_quality_*
+ *   lig_res_first [R_l + 1], rec_res_first [R_r + 1]  int32: the first atom row (global) of every residue (the kernels hold
+ *     every range inside the complex's rows whatever the table says)
+ *   sphere [n_points][3] fp64: unit vectors u_k supplied by the caller, 1 <= n_points <= EQD_DOCK_SASA_MAX_POINTS
+ *   probe fp64, finite and > 0
+ * Definitions.
+ *   Expanded radius  R_i = (double)r_i + probe.
+ *   Burial           point k of atom i is q = x_i + R_i * u_k per component (one multiply, then one add).  It is buried by
+ *                    atom j != i when s = (dx * dx + dy * dy) + dz * dz < R_j * R_j with d = q - x_j.
+ *   Counts           every atom has two counts of exposed points: alone (j ranges over the atom's own side) and in complex
+ *                    (j ranges over both sides of its complex).  Both come from one walk: same-side partners first, the
+ *                    other side only for points still exposed.
+ *   Areas            of an atom (4 * pi * R_i * R_i / n_points) * n_i, evaluated left to right; of a residue the sum over
+ *                    its atoms in row order; of a side and of the complex the sum over the atoms in row order, ligand
+ *                    before receptor; BSA the sum of (4 * pi * R_i * R_i / n_points) * (n_alone_i - n_complex_i) in the
+ *                    same order - no cancellation, every term >= 0.
+ *   Skipping         a partner is left out of an atom's walk only when it provably buries nothing: the squared centre
+ *                    distance (the expression s above on the centres) is >= (R_i + R_j + 1e-6)^2; a whole residue is passed
+ *                    over only by a bound on its atoms that implies this for each of them.  The kept partners of an
+ *                    atom go on a list of fixed capacity; an atom with more partners than that walks ALL atoms of its
+ *                    complex instead, and all_partners != 0 sends every atom down that path.  Both paths give the same
+ *                    integers and therefore the same bits, on any input.
+ * Outputs.
+ *   lig_points [A_l][2], rec_points [A_r][2] int32: exposed points alone, in complex
+ *   lig_res_area [R_l][2], rec_res_area [R_r][2] fp64: residue area alone, in complex
+ *   rows [C][EQD_DOCK_SASA_COLS] fp64:
+ *     0 SASA of the ligand alone, 1 SASA of the receptor alone, 2 SASA of the complex, 3 BSA, 4 / 5 the ligand's / the
+ *     receptor's share of the BSA, 6 / 7 buried atoms (n_alone > n_complex) of the ligand / receptor, 8 / 9 buried
+ *     residues (>= 1 buried atom) of the ligand / receptor, 10 / 11 exposed points of all atoms alone / in complex
+ *     (columns 6-11 are integers stored as fp64)
+ * Sequence: workspace_bytes -> init (once per set of offsets) -> eval (any number of times).
+ */
+#define EQD_DOCK_SASA_ABI 1
+#define EQD_DOCK_SASA_COLS 12
+#define EQD_DOCK_SASA_MAX_POINTS 1024
+EQD_DOCK_API int eqd_dock_sasa_abi(void);
+
+/* Workspace of a batch with these host offsets; 0 when they are invalid, do not fit 32-bit offsets or n_points is outside
+ * 1..EQD_DOCK_SASA_MAX_POINTS (eqd_dock_last_error says why). */
+EQD_DOCK_API size_t eqd_dock_sasa_workspace_bytes(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                                  const int32_t* lig_res_off, const int32_t* rec_res_off, int n_points);
+
+/* Validates the offsets and writes the batch's work-item table into the workspace (a host-to-device copy; this call
+ * waits for that copy). */
+EQD_DOCK_API int eqd_dock_sasa_init(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                    const int32_t* lig_res_off, const int32_t* rec_res_off, int n_points, void* workspace,
+                                    size_t ws_bytes, void* stream);
+
+/* Enqueues the surface pass (five launches, whatever C is) on a workspace prepared by eqd_dock_sasa_init with the same
+ * offsets.  No synchronisation, no allocation, no host-device copy: the call can be captured into a hipGraph.  Invalid
+ * offsets, n_points outside 1..EQD_DOCK_SASA_MAX_POINTS, a probe that is not finite and > 0 or a workspace that is too
+ * small return an EQD_ERR_* code; nothing is launched then. */
+EQD_DOCK_API int eqd_dock_sasa_eval(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                    const int32_t* lig_res_off, const int32_t* rec_res_off, const float* lig,
+                                    const float* rec, const float* lig_radius, const float* rec_radius,
+                                    const int32_t* lig_res_first, const int32_t* rec_res_first, const double* sphere,
+                                    int n_points, double probe, int all_partners, int32_t* lig_points, int32_t* rec_points,
+                                    double* lig_res_area, double* rec_res_area, double* rows, void* workspace,
+                                    size_t ws_bytes, void* stream);
+
+/*
  * Batched exact transport plans: the solver call of the pocket OT term, src/utils/ot_utils.py:22-29 (POT's
  * ot.emd(a, b, M) with uniform a = 1/n, b = 1/m), for P problems in ONE launch - the call that replaces the host solver
  * eqd_host_emd_uniform (csrc_host/eqd_host_emd.cpp) and the device <-> host round trip around it.  The algorithm is the
