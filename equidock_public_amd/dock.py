@@ -6,6 +6,9 @@
         its own  ->  with ground truth: ligand / complex / interface RMSD of ALL complexes in one device pass
         (rmsd_metrics_batch)  ->  PDB files and the CRMSD / IRMSD summary
 
+Evaluation passes over every heavy atom, one batched device pass each: `pose_quality_batch` (fnat, LRMSD, backbone iRMSD,
+DockQ, clashes), `surface_area_batch` (SASA, buried surface area) and `lddt_batch` (lDDT, interface lDDT, per-residue scores).
+
 `remove_clashes_batch` is `inference.remove_clashes` for a list of complexes: same keys, same stop rule, same meaning;
 `rmsd_metrics_batch` / `DeviceMeter` are `inference.rmsd_metrics` + `complex_and_interface_rmsd` /
 `inference.Meter_Unbound_Bound` for a list of complexes, results on the device; `dock_complexes` is the Python API, `python -m equidock_public_amd.dock` the command-line counterpart of
@@ -37,6 +40,9 @@ EMD_RESIDENT_CELLS = 8192  # EQD_DOCK_EMD_RESIDENT_CELLS
 DOCK_SASA_ABI = 1
 SASA_COLS = 12             # EQD_DOCK_SASA_COLS
 SASA_MAX_POINTS = 1024     # EQD_DOCK_SASA_MAX_POINTS
+DOCK_LDDT_ABI = 1
+LDDT_COLS = 16             # EQD_DOCK_LDDT_COLS
+LDDT_BLOCK = 64            # EQD_DOCK_LDDT_BLOCK
 
 _dock = None
 _dock_is_sim = False
@@ -91,6 +97,14 @@ def _declare(lib):
     lib.eqd_dock_sasa_eval.restype = C.c_int
     lib.eqd_dock_sasa_eval.argtypes = ([C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 6 +
                                        [C.c_size_t, C.c_void_p])
+    lib.eqd_dock_lddt_abi.restype = C.c_int
+    lib.eqd_dock_lddt_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_lddt_workspace_bytes.argtypes = [C.c_int] + [C.c_void_p] * 4
+    lib.eqd_dock_lddt_init.restype = C.c_int
+    lib.eqd_dock_lddt_init.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]
+    lib.eqd_dock_lddt_eval.restype = C.c_int
+    lib.eqd_dock_lddt_eval.argtypes = ([C.c_int] + [C.c_void_p] * 10 + [C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                       [C.c_size_t, C.c_void_p])
     lib.eqd_dock_emd_abi.restype = C.c_int
     lib.eqd_dock_emd_workspace_bytes.restype = C.c_size_t
     lib.eqd_dock_emd_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_int]
@@ -117,6 +131,8 @@ def _bind(path):
         raise _lib.EquidockHipError(f"{path}: dock EMD ABI {lib.eqd_dock_emd_abi()} != {DOCK_EMD_ABI}")
     if lib.eqd_dock_sasa_abi() != DOCK_SASA_ABI:
         raise _lib.EquidockHipError(f"{path}: dock SASA ABI {lib.eqd_dock_sasa_abi()} != {DOCK_SASA_ABI}")
+    if lib.eqd_dock_lddt_abi() != DOCK_LDDT_ABI:
+        raise _lib.EquidockHipError(f"{path}: dock lDDT ABI {lib.eqd_dock_lddt_abi()} != {DOCK_LDDT_ABI}")
     _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
     return lib
 
@@ -772,6 +788,143 @@ def surface_area_batch(lig_list, rec_list, lig_radii=None, rec_radii=None, lig_r
     return res
 
 
+# ---- batched lDDT and interface lDDT --------------------------------------------------------------------------------
+LDDT_KEYS = ('lddt', 'ilddt', 'lddt_ligand', 'lddt_receptor', 'pairs', 'interface_pairs', 'preserved_0', 'preserved_1',
+             'preserved_2', 'preserved_3', 'interface_preserved_0', 'interface_preserved_1', 'interface_preserved_2',
+             'interface_preserved_3', 'skipped_block_pairs')
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+
+
+def lddt_pruning_enabled():
+    """EQD_DOCK_LDDT_PRUNE=0 turns the centroid-and-radius bound on block pairs of the lDDT pass off (same results but for
+    the count of skipped block pairs)."""
+    return os.environ.get('EQD_DOCK_LDDT_PRUNE', '1') != '0'
+
+
+class LddtPlan:
+    """Workspace and tables of eqd_dock_lddt_eval for one batch of complexes: the per-complex residue offsets (local:
+    [n_res + 1] into the complex's own rows) go up in ONE copy, the workspace is created and initialised once (init copies
+    the item table and waits for that copy); `eval` then only enqueues launches - it can be captured into a hipGraph."""
+
+    def __init__(self, lig_res_offsets, rec_res_offsets, dev):
+        lib = load_dock_library()
+        n = len(lig_res_offsets)
+        if n == 0 or n != len(rec_res_offsets):
+            raise ValueError(f"{n} ligand residue tables for {len(rec_res_offsets)} receptor residue tables")
+        # (a table's last entry is its side's atom count; lddt_batch compares it with the rows it is given)
+        lro = [_residue_table(o, int(np.asarray(o).reshape(-1)[-1:].sum()), f'complex {c}: ligand')
+               for c, o in enumerate(lig_res_offsets)]
+        rro = [_residue_table(o, int(np.asarray(o).reshape(-1)[-1:].sum()), f'complex {c}: receptor')
+               for c, o in enumerate(rec_res_offsets)]
+        self.n, self.dev = n, torch.device(dev)
+        _require_device(torch.empty(0, device=self.dev), 'lDDT inputs')
+        self.lig_atom_off, self.rec_atom_off = _offsets([int(o[-1]) for o in lro]), _offsets([int(o[-1]) for o in rro])
+        self.lig_res_off, self.rec_res_off = _offsets([len(o) - 1 for o in lro]), _offsets([len(o) - 1 for o in rro])
+        self._off = tuple(a.ctypes.data_as(C.c_void_p) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off,
+                                                                  self.rec_res_off))
+        Al, Ar, Rl, Rr = (int(a[-1]) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off, self.rec_res_off))
+        self.sizes = (Al, Ar, Rl, Rr)
+        # one staging buffer, one upload: int32 first rows of the ligand | of the receptor residues
+        host = _staging(Rl + Rr + 2, torch.int32, self.dev)
+        first = host.numpy()
+        first[:Rl + 1] = np.concatenate([o[:-1] + int(a) for o, a in zip(lro, self.lig_atom_off)] + [[Al]])
+        first[Rl + 1:] = np.concatenate([o[:-1] + int(a) for o, a in zip(rro, self.rec_atom_off)] + [[Ar]])
+        self.tables = host.to(self.dev, non_blocking=True)
+        self.lig_first, self.rec_first = self.tables[:Rl + 1], self.tables[Rl + 1:]
+        n_at = np.diff(self.lig_atom_off).astype(np.int64) + np.diff(self.rec_atom_off).astype(np.int64)
+        self.atom_pairs = int((n_at * (n_at - 1)).sum())
+        self.wsb = lib.eqd_dock_lddt_workspace_bytes(n, *self._off)
+        if self.wsb == 0:
+            check(2)
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        with _lib.device_guard(self.dev):
+            check(lib.eqd_dock_lddt_init(n, *self._off, _lib.ptr(self.ws), C.c_size_t(self.wsb), _stream(self.dev)))
+
+    def outputs(self):
+        """Freshly allocated output buffers of one eval: (counts [A_l + A_r][10] int32, residue scores [R_l + R_r][2] fp64,
+        rows [C][16] fp64); the ligand's rows come first in the first two."""
+        Al, Ar, Rl, Rr = self.sizes
+        return (torch.empty(Al + Ar, 10, dtype=torch.int32, device=self.dev),
+                torch.empty(Rl + Rr, 2, dtype=torch.float64, device=self.dev),
+                torch.empty(self.n, LDDT_COLS, dtype=torch.float64, device=self.dev))
+
+    def eval(self, lig_pred, rec_pred, lig_true, rec_true, counts, res_lddt, rows, inclusion_radius=15.0,
+             thresholds=LDDT_THRESHOLDS, prune=None):
+        """Enqueue the lDDT pass on the current stream: [sum n][3] fp32 contiguous inputs (rec_pred may be None: it is
+        rec_true), the buffers of `outputs()`.  No synchronisation, no allocation, no copy."""
+        Al, Ar, Rl, Rr = self.sizes
+        prune = lddt_pruning_enabled() if prune is None else bool(prune)
+        thr = [float(t) for t in thresholds]
+        if len(thr) != 4:
+            raise ValueError(f"{len(thr)} thresholds (need 4)")
+        with _lib.device_guard(self.dev):
+            check(_dock.eqd_dock_lddt_eval(self.n, *self._off, _lib.ptr(lig_pred),
+                                           _lib.ptr(rec_pred) if rec_pred is not None else C.c_void_p(0),
+                                           _lib.ptr(lig_true), _lib.ptr(rec_true), _lib.ptr(self.lig_first),
+                                           _lib.ptr(self.rec_first), C.c_double(float(inclusion_radius)),
+                                           (C.c_double * 4)(*thr), int(prune), _lib.ptr(counts[:Al]), _lib.ptr(counts[Al:]),
+                                           _lib.ptr(res_lddt[:Rl]), _lib.ptr(res_lddt[Rl:]), _lib.ptr(rows),
+                                           _lib.ptr(self.ws), C.c_size_t(self.wsb), _stream(self.dev)))
+        return rows
+
+
+def lddt_batch(lig_pred_list, lig_true_list, rec_true_list, lig_res_offsets=None, rec_res_offsets=None, rec_pred_list=None,
+               inclusion_radius=15.0, thresholds=LDDT_THRESHOLDS, plan=None):
+    """lDDT (Mariani et al. 2013) and interface lDDT of C docked complexes in one device pass over every heavy atom
+    (eqd_dock_lddt_*; the definitions are in include/equidock_dock.h): the fraction of the native's atom pairs in
+    different residues and closer than `inclusion_radius` whose distance the model keeps within each of the four
+    `thresholds`, averaged over them - over all pairs and over the inter-chain pairs alone.  No superposition is involved.
+    The lists hold device tensors [n_c, 3] of heavy atoms, the model's rows corresponding one to one to the native's;
+    `rec_pred_list` None: the model's receptor is the native's.  Per complex (host arrays, as `atom_table` returns them)
+    the residue offsets [n_res + 1] into its own rows of each side - or a `plan` (LddtPlan) that already holds them, so
+    that repeated evaluation of the same complexes reuses tables and workspace.  fp64 on the device from the fp32 rows;
+    every result is a count or a quotient of counts: a complex's results are bit-identical alone, in any batch and from run
+    to run.
+
+    Returns a dict of device tensors: LDDT_KEYS (float64 [C]: lddt, ilddt, lddt_ligand, lddt_receptor - NaN without an
+    included pair -, pairs, interface_pairs, preserved_0..3, interface_preserved_0..3, skipped_block_pairs), `rows`, the
+    raw [C][16] buffer, `lig_counts` / `rec_counts` (int32 [A][10]: n_all, p_all[4], n_inter, p_inter[4]), `lig_res_lddt` /
+    `rec_res_lddt` (float64 [R][2]: residue lDDT, residue interface lDDT) and `plan`.  One upload of the small tables
+    (when no plan is given), one launch sequence; apart from the item-table copy of the workspace's init the call does not
+    synchronise and downloads nothing."""
+    ligs_p, ligs_t, recs_t = list(lig_pred_list), list(lig_true_list), list(rec_true_list)
+    recs_p = None if rec_pred_list is None else list(rec_pred_list)
+    n = len(ligs_p)
+    if not (n == len(ligs_t) == len(recs_t)) or (recs_p is not None and len(recs_p) != n):
+        raise ValueError(f"{n} predicted ligands for {len(ligs_t)} true ligands, {len(recs_t)} true receptors and "
+                         f"{'no' if recs_p is None else len(recs_p)} predicted receptors")
+    if n == 0:
+        raise ValueError("lddt_batch: no complexes")
+    ligs_p, ligs_t, recs_t = _meter_rows(ligs_p, 'predicted ligand'), _meter_rows(ligs_t, 'true ligand'), _meter_rows(recs_t, 'true receptor')
+    if recs_p is not None:
+        recs_p = _meter_rows(recs_p, 'predicted receptor')
+    for c in range(n):
+        if ligs_p[c].shape[0] != ligs_t[c].shape[0]:
+            raise ValueError(f"complex {c}: {ligs_p[c].shape[0]} predicted ligand rows for {ligs_t[c].shape[0]} true ones")
+        if recs_p is not None and recs_p[c].shape[0] != recs_t[c].shape[0]:
+            raise ValueError(f"complex {c}: {recs_p[c].shape[0]} predicted receptor rows for {recs_t[c].shape[0]} true ones")
+    dev = ligs_p[0].device
+    if plan is None:
+        if lig_res_offsets is None or rec_res_offsets is None:
+            raise ValueError("lddt_batch: residue offsets of both sides (or a plan) are needed")
+        plan = LddtPlan(list(lig_res_offsets), list(rec_res_offsets), dev)
+    if plan.n != n:
+        raise ValueError(f"the plan holds {plan.n} complexes, the lists {n}")
+    for c in range(n):
+        nl, nr = int(plan.lig_atom_off[c + 1] - plan.lig_atom_off[c]), int(plan.rec_atom_off[c + 1] - plan.rec_atom_off[c])
+        if ligs_t[c].shape[0] != nl or recs_t[c].shape[0] != nr:
+            raise ValueError(f"complex {c}: {ligs_t[c].shape[0]} ligand and {recs_t[c].shape[0]} receptor rows for tables of "
+                             f"{nl} and {nr} atoms")
+    counts, res_lddt, rows = plan.outputs()
+    plan.eval(torch.cat(ligs_p, 0), None if recs_p is None else torch.cat(recs_p, 0), torch.cat(ligs_t, 0),
+              torch.cat(recs_t, 0), counts, res_lddt, rows, inclusion_radius=inclusion_radius, thresholds=thresholds)
+    Al, Rl = plan.sizes[0], plan.sizes[2]
+    res = {k: rows[:, i] for i, k in enumerate(LDDT_KEYS)}
+    res.update(rows=rows, lig_counts=counts[:Al], rec_counts=counts[Al:], lig_res_lddt=res_lddt[:Rl],
+               rec_res_lddt=res_lddt[Rl:], plan=plan)
+    return res
+
+
 # ---- batched graph construction -------------------------------------------------------------------------------------
 GRAPH_KEYS = ('x', 'res_feat', 'mu_r_norm', 'src', 'dst', 'he')
 last_graph_stats = {}      # of the latest protein_graphs_batch call: proteins, residues, edges, pairs, pruned_pairs, pruning
@@ -965,10 +1118,11 @@ def _chunk_metrics(chunk, truths, first, final_lig, rec_atoms, cutoff, dev):
     return rmsd_metrics_batch(lig_pred, lig_true, rec_true, cutoff=cutoff, interface=True)['metrics'].cpu().numpy()
 
 
-def _chunk_quality(chunk, truths, first, final_lig, rec_atoms, cuts, dev):
-    """The quality stage of dock_complexes for one chunk: the heavy-atom rows of the final ligands and of the receptors
-    taken on the device by an index built on the host, one pose_quality_batch (the model's receptor is the receptor given),
-    ONE download of the [C][16] rows - a download of its own, after the meter's."""
+def _chunk_heavy_rows(chunk, truths, first, final_lig, rec_atoms, dev):
+    """The heavy-atom rows of a chunk's final ligands and receptors, taken on the device by an index built on the host, and
+    the heavy atoms of the ground-truth ligands in one upload: (ligand tables, receptor tables - as atom_table returns them
+    -, model ligands, native ligands, receptors).  A ligand whose heavy-atom names differ from its ground truth's raises
+    ValueError naming the complex."""
     lig_t, rec_t, gts = [], [], []
     for k, ((lig_in, rec_in), gt) in enumerate(zip(chunk, truths)):
         lig_t.append(atom_table(lig_in))
@@ -991,9 +1145,25 @@ def _chunk_quality(chunk, truths, first, final_lig, rec_atoms, cuts, dev):
     lig_pred = [final_lig[k].index_select(0, didx[ioff[k]:ioff[k + 1]]) for k in range(n)]
     rec_true = [rec_atoms[k].index_select(0, didx[ioff[n + k]:ioff[n + k + 1]]) for k in range(n)]
     lig_true = [dgt[goff[k]:goff[k + 1]] for k in range(n)]
+    return lig_t, rec_t, lig_pred, lig_true, rec_true
+
+
+def _chunk_quality(chunk, truths, first, final_lig, rec_atoms, cuts, dev):
+    """The quality stage of dock_complexes for one chunk: the heavy-atom rows of the final ligands and of the receptors
+    taken on the device by an index built on the host, one pose_quality_batch (the model's receptor is the receptor given),
+    ONE download of the [C][16] rows - a download of its own, after the meter's."""
+    lig_t, rec_t, lig_pred, lig_true, rec_true = _chunk_heavy_rows(chunk, truths, first, final_lig, rec_atoms, dev)
     q = pose_quality_batch(lig_pred, lig_true, rec_true, [t[2] for t in lig_t], [t[2] for t in rec_t], [t[3] for t in lig_t],
                            [t[3] for t in rec_t], contact_cutoff=cuts[0], interface_cutoff=cuts[1], clash_cutoff=cuts[2])
     return q['quality'].cpu().numpy()
+
+
+def _chunk_lddt(chunk, truths, first, final_lig, rec_atoms, radius, dev):
+    """The lDDT stage of dock_complexes for one chunk: the rows of `_chunk_heavy_rows`, one lddt_batch (the model's receptor
+    is the receptor given), ONE download of the [C][16] rows."""
+    lig_t, rec_t, lig_pred, lig_true, rec_true = _chunk_heavy_rows(chunk, truths, first, final_lig, rec_atoms, dev)
+    return lddt_batch(lig_pred, lig_true, rec_true, [t[2] for t in lig_t], [t[2] for t in rec_t],
+                      inclusion_radius=radius)['rows'].cpu().numpy()
 
 
 def _chunk_surface(chunk, truths, first, final_lig, rec_atoms, probe, n_points, dev):
@@ -1061,7 +1231,8 @@ def _chunk_graphs(chunk, cutoff, max_neighbor, dev):
 def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=None, device=None, cutoff=30.0,
                    max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50,
                    batched_graphs=True, ground_truth=None, interface_cutoff=8.0, quality=False,
-                   quality_cutoffs=(5.0, 10.0, 3.0), surface=False, surface_probe=1.4, surface_points=96):
+                   quality_cutoffs=(5.0, 10.0, 3.0), surface=False, surface_probe=1.4, surface_points=96, lddt=False,
+                   lddt_radius=15.0):
     """Dock a list of (ligand, receptor) complexes, each side a PDB path or a list of featurize.Residue (the ligand's
     file / residues in their input pose, the receptor's in the bound pose - the reference's `*_l_b.pdb` and
     `*_r_b_COMPLEX.pdb`).  Per chunk of `max_complexes_per_batch` complexes (all at once by default): graphs on the
@@ -1092,10 +1263,18 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
     and one more download, and the results gain `sasa_ligand`, `sasa_receptor`, `sasa_complex`, `bsa` (floats, square
     Angstrom), `buried_atoms_ligand`, `buried_atoms_receptor`, `buried_residues_ligand` and `buried_residues_receptor`
     (ints); batch_seconds gains 'surface'.  With `ground_truth` the native ligands go into the same batch as C more
-    complexes and the results gain `bsa_native`.  surface=False changes nothing."""
+    complexes and the results gain `bsa_native`.  surface=False changes nothing.
+
+    `lddt` (needs `ground_truth`): each chunk also ends with one lddt_batch over EVERY heavy atom of its final ligands
+    (the rows and the heavy-atom-name check of `quality`; the model's receptor is the receptor given; inclusion radius
+    `lddt_radius`, thresholds 0.5, 1, 2 and 4 Angstrom) and one more download, and the results gain `lddt`, `ilddt`
+    (floats; ilddt NaN when no inter-chain atom pair of the native is closer than the radius), `lddt_pairs` and
+    `ilddt_pairs` (ints: the included ordered atom pairs); batch_seconds gains 'lddt'.  lddt=False changes nothing."""
     complexes = list(complexes)
     if quality and ground_truth is None:
         raise ValueError("quality=True needs ground_truth")
+    if lddt and ground_truth is None:
+        raise ValueError("lddt=True needs ground_truth")
     if ground_truth is not None:
         ground_truth = list(ground_truth)
         if len(ground_truth) != len(complexes):
@@ -1143,7 +1322,7 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
             t4 = time.perf_counter()
             times = {'graphs': t1 - t0, 'model': t2 - t1, 'rigid': t3 - t2, 'clashes': t4 - t3, 'total': t4 - t0,
                      'n_complexes': len(chunk)}
-            rows = qrows = srows = None
+            rows = qrows = srows = lrows = None
             if ground_truth is not None:
                 final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
                 rows = _chunk_metrics(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, interface_cutoff, dev)
@@ -1153,6 +1332,11 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                     qrows = _chunk_quality(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, quality_cutoffs, dev)
                     t6 = time.perf_counter()       # (the download has synchronised)
                     times.update(quality=t6 - t5, total=t6 - t0)
+                if lddt:
+                    tl = time.perf_counter()       # (every earlier stage has synchronised)
+                    lrows = _chunk_lddt(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, lddt_radius, dev)
+                    tm = time.perf_counter()       # (the download has synchronised)
+                    times.update(lddt=tm - tl, total=tm - t0)
             if surface:
                 final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
                 ts = time.perf_counter()           # (every earlier stage has synchronised)
@@ -1183,6 +1367,9 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                                        buried_residues_ligand=int(s[8]), buried_residues_receptor=int(s[9]))
                     if ground_truth is not None:
                         results[-1].update(bsa_native=float(srows[len(chunk) + i, 3]))
+                if lrows is not None:
+                    results[-1].update(lddt=float(lrows[i, 0]), ilddt=float(lrows[i, 1]), lddt_pairs=int(lrows[i, 4]),
+                                       ilddt_pairs=int(lrows[i, 5]))
     finally:
         net.train(was_training)
     return results
@@ -1219,6 +1406,9 @@ def main(argv=None):
                    help='solvent-accessible surface of every docked pose from one batched device pass per batch over every '
                         'heavy atom: buried surface area and buried residues (needs no ground truth; when every '
                         '<name>_l_b_COMPLEX.pdb is present, the native BSA as well)')
+    p.add_argument('--lddt', action='store_true',
+                   help='lDDT and interface lDDT of every docked pose against its native from one batched device pass per '
+                        'batch over every heavy atom (needs every <name>_l_b_COMPLEX.pdb)')
     a = p.parse_args(argv)
     try:
         names = sorted(os.path.basename(f)[:-len('_l_b.pdb')] for f in glob.glob(os.path.join(a.input_dir, '*_l_b.pdb')))
@@ -1231,12 +1421,12 @@ def main(argv=None):
                 raise FileNotFoundError(f"{rec} is missing (receptor of {nm})")
             complexes.append((os.path.join(a.input_dir, nm + '_l_b.pdb'), rec))
         truths = None
-        if a.device_metrics or a.dockq:
+        if a.device_metrics or a.dockq or a.lddt:
             truths = [os.path.join(a.gt_dir, nm + '_l_b_COMPLEX.pdb') for nm in names]
             for gt in truths:
                 if not os.path.isfile(gt):
-                    raise FileNotFoundError(f"{gt} is missing ({'--device-metrics' if a.device_metrics else '--dockq'} "
-                                            "needs the ground-truth ligand of every complex)")
+                    flag = '--device-metrics' if a.device_metrics else '--dockq' if a.dockq else '--lddt'
+                    raise FileNotFoundError(f"{gt} is missing ({flag} needs the ground-truth ligand of every complex)")
         if a.surface and truths is None:
             gts = [os.path.join(a.gt_dir, nm + '_l_b_COMPLEX.pdb') for nm in names]
             truths = gts if all(os.path.isfile(g) for g in gts) else None
@@ -1248,9 +1438,10 @@ def main(argv=None):
         res = dock_complexes(net, complexes, remove_clashes=a.remove_clashes, max_complexes_per_batch=a.batch or None,
                              device=dev, cutoff=float(ca.get('graph_cutoff', 30.0)),
                              max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it,
-                             batched_graphs=not a.no_batched_graphs, ground_truth=truths, quality=a.dockq, surface=a.surface)
+                             batched_graphs=not a.no_batched_graphs, ground_truth=truths, quality=a.dockq, surface=a.surface,
+                             lddt=a.lddt)
         suffix = '_EQUIDOCK_NO_CLASHES.pdb' if a.remove_clashes else '_EQUIDOCK.pdb'
-        crmsd, irmsd, dockq, bsa, bsa_native = [], [], [], [], []
+        crmsd, irmsd, dockq, bsa, bsa_native, ilddt = [], [], [], [], [], []
         for nm, (lig_path, rec_path), r in zip(names, complexes, res):
             out = os.path.join(a.out_dir, nm + '_l_b' + suffix)
             INF.write_pdb_coordinates(lig_path, r['ligand_atoms'], out)
@@ -1280,6 +1471,9 @@ def main(argv=None):
                 if 'bsa_native' in r:
                     bsa_native.append(r['bsa_native'])
                     line += f"  native BSA {r['bsa_native']:.1f}"
+            if a.lddt:
+                ilddt.append(r['ilddt'])
+                line += f"  lDDT {r['lddt']:.4f}  ilDDT {r['ilddt']:.4f}"
             print(line, flush=True)
         wall = time.perf_counter() - t0
         print(f"Mean runtime: {wall / len(res):.4f} s per complex ({len(res)} complexes, {wall:.3f} s)")
@@ -1297,6 +1491,11 @@ def main(argv=None):
             print("BSA median/mean/std: %.1f / %.1f / %.1f" % _stats(bsa))
         if bsa_native:
             print("native BSA median/mean/std: %.1f / %.1f / %.1f" % _stats(bsa_native))
+        if a.lddt:
+            il = np.asarray(ilddt, dtype=np.float64)
+            ok = il[~np.isnan(il)]                  # (undefined without an inter-chain atom pair under the radius)
+            print("ilDDT median/mean/std: %.4f / %.4f / %.4f" % (_stats(ok) if ok.size else (float('nan'),) * 3) +
+                  ("  undefined %d" % (il.size - ok.size) if ok.size < il.size else ""))
     except Exception as e:          # noqa: BLE001 - a command-line tool: report and exit non-zero
         print(f"error: {type(e).__name__}: {e}", file=sys.stderr)
         return 1

@@ -271,6 +271,77 @@ EQD_DOCK_API int eqd_dock_sasa_eval(int n_complex, const int32_t* lig_atom_off, 
                                     size_t ws_bytes, void* stream);
 
 /*
+ * Batched lDDT and interface lDDT (Mariani et al. 2013): the superposition-free, atom-level comparison of a model with its
+ * native over EVERY heavy atom of C complexes in one device pass - per atom the distances to its native neighbours that
+ * the model preserves, from which the lDDT of each residue, of each partner and of the complex follow, and the same
+ * restricted to inter-chain pairs (interface lDDT).  fp64 arithmetic from the fp32 inputs, without contraction, exactly as
+ * written below; every result is a count of threshold decisions, so a complex's results are bit-identical alone, in any
+ * batch, at any position, with prune on or off and from run to run.
+ *
+ * Layout: that of eqd_dock_quality_*; the complexes are stored one after another and the model's rows correspond one to
+ * one to the native's.  The atoms of complex c are its ligand rows followed by its receptor rows.
+ *   lig_pred, lig_true [A_l][3] fp32, rec_pred, rec_true [A_r][3] fp32 (rec_pred may be NULL: the model's receptor is rec_true)
+ *   lig_atom_off / rec_atom_off / lig_res_off / rec_res_off [C + 1]  HOST int32, as for eqd_dock_quality_*
+ *   lig_res_first [R_l + 1], rec_res_first [R_r + 1]  int32: the first atom row (global) of every residue (an atom belongs
+ *     to the last residue of its complex and side whose first row is not behind it, whatever else the table says)
+ *   inclusion_radius fp64 and thresholds[4] HOST fp64 t_0..t_3, each finite and > 0 (usually 15 and 0.5, 1, 2, 4 Angstrom)
+ * Definitions.
+ *   Distance         d(i, j) = sqrt((dx * dx + dy * dy) + dz * dz); d_n in the native, d_m in the model.
+ *   Included pair    an ordered pair (i, j) of atoms of the same complex that lie in different residues, with
+ *                    d_n(i, j) < inclusion_radius.  Two atoms of one entry of a residue table are in the same residue, a
+ *                    ligand residue never equals a receptor residue; every unordered pair is counted twice, once for each
+ *                    of its atoms.
+ *   Preserved        at threshold k when fabs(d_m - d_n) < t_k.
+ *   Counts           per atom ten int32: n_all (included partners), p_all[4] (partners preserved per threshold), n_inter,
+ *                    p_inter[4] (the same, restricted to partners on the other side).
+ *   Score            of any set of atoms (a residue, a side, the complex): (double)(P0 + P1 + P2 + P3) / (4.0 * (double)N)
+ *                    with N and P_k the 64-bit integer sums of the atoms' counts; NaN when N == 0.
+ *   Pruning          (prune != 0) the rows of each side of a complex are cut into blocks of EQD_DOCK_LDDT_BLOCK consecutive
+ *                    rows (the last block of a side may be short).  A block has a native centroid - the row-order fp64 sum
+ *                    divided by the count - and a radius, the largest d from the centroid to a row.  An ordered block pair
+ *                    (a, b) is not evaluated when (d(centroids) - r_a) - r_b >= inclusion_radius + 1e-6: no atom pair of it
+ *                    can be included.  Inside an evaluated block pair the square root is skipped only where
+ *                    s >= (inclusion_radius + 1e-6)^2 proves the pair is not included; every decision that counts is made
+ *                    with the expressions above.
+ * Outputs.
+ *   lig_counts [A_l][10], rec_counts [A_r][10] int32: n_all, p_all[4], n_inter, p_inter[4]
+ *   lig_res_lddt [R_l][2], rec_res_lddt [R_r][2] fp64: residue lDDT, residue interface lDDT
+ *   rows [C][EQD_DOCK_LDDT_COLS] fp64:
+ *     0 lDDT (all pairs), 1 interface lDDT (inter-chain pairs only), 2 / 3 lDDT over the ligand's / the receptor's atoms,
+ *     4 N (all pairs), 5 N (inter-chain pairs), 6-9 P_k (all pairs), 10-13 P_k (inter-chain pairs), 14 ordered block pairs
+ *     skipped by the bound (0 with prune == 0; no other output depends on prune), 15: 0 (columns 4-14 are integers stored
+ *     as fp64)
+ * Sequence: workspace_bytes -> init (once per set of offsets) -> eval (any number of times).
+ */
+#define EQD_DOCK_LDDT_ABI 1
+#define EQD_DOCK_LDDT_COLS 16
+#define EQD_DOCK_LDDT_BLOCK 64
+EQD_DOCK_API int eqd_dock_lddt_abi(void);
+
+/* Workspace of a batch with these host offsets; 0 when they are invalid or do not fit 32-bit offsets
+ * (eqd_dock_last_error says why). */
+EQD_DOCK_API size_t eqd_dock_lddt_workspace_bytes(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                                  const int32_t* lig_res_off, const int32_t* rec_res_off);
+
+/* Validates the offsets and writes the batch's work-item table into the workspace (a host-to-device copy; this call
+ * waits for that copy). */
+EQD_DOCK_API int eqd_dock_lddt_init(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                    const int32_t* lig_res_off, const int32_t* rec_res_off, void* workspace, size_t ws_bytes,
+                                    void* stream);
+
+/* Enqueues the lDDT pass (four launches, whatever C is) on a workspace prepared by eqd_dock_lddt_init with the same
+ * offsets.  No synchronisation, no allocation, no host-device copy: the call can be captured into a hipGraph.  Invalid
+ * offsets, an inclusion_radius or a threshold that is not finite and > 0, or a workspace that is too small return an
+ * EQD_ERR_* code; nothing is launched then. */
+EQD_DOCK_API int eqd_dock_lddt_eval(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                    const int32_t* lig_res_off, const int32_t* rec_res_off, const float* lig_pred,
+                                    const float* rec_pred, const float* lig_true, const float* rec_true,
+                                    const int32_t* lig_res_first, const int32_t* rec_res_first, double inclusion_radius,
+                                    const double* thresholds, int prune, int32_t* lig_counts, int32_t* rec_counts,
+                                    double* lig_res_lddt, double* rec_res_lddt, double* rows, void* workspace,
+                                    size_t ws_bytes, void* stream);
+
+/*
  * Batched exact transport plans: the solver call of the pocket OT term, src/utils/ot_utils.py:22-29 (POT's
  * ot.emd(a, b, M) with uniform a = 1/n, b = 1/m), for P problems in ONE launch - the call that replaces the host solver
  * eqd_host_emd_uniform (csrc_host/eqd_host_emd.cpp) and the device <-> host round trip around it.  The algorithm is the
