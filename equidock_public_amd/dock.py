@@ -7,7 +7,9 @@
         (rmsd_metrics_batch)  ->  PDB files and the CRMSD / IRMSD summary
 
 Evaluation passes over every heavy atom, one batched device pass each: `pose_quality_batch` (fnat, LRMSD, backbone iRMSD,
-DockQ, clashes), `surface_area_batch` (SASA, buried surface area) and `lddt_batch` (lDDT, interface lDDT, per-residue scores).
+DockQ, clashes), `surface_area_batch` (SASA, buried surface area), `lddt_batch` (lDDT, interface lDDT, per-residue scores)
+and `residue_depth_batch` (atom and residue depth below the surface, alone and in complex); `surface_feature_analysis` is
+src/surface_analysis.py on top of the last one.
 
 `remove_clashes_batch` is `inference.remove_clashes` for a list of complexes: same keys, same stop rule, same meaning;
 `rmsd_metrics_batch` / `DeviceMeter` are `inference.rmsd_metrics` + `complex_and_interface_rmsd` /
@@ -43,6 +45,8 @@ SASA_MAX_POINTS = 1024     # EQD_DOCK_SASA_MAX_POINTS
 DOCK_LDDT_ABI = 1
 LDDT_COLS = 16             # EQD_DOCK_LDDT_COLS
 LDDT_BLOCK = 64            # EQD_DOCK_LDDT_BLOCK
+DOCK_DEPTH_ABI = 1
+DEPTH_COLS = 16            # EQD_DOCK_DEPTH_COLS
 
 _dock = None
 _dock_is_sim = False
@@ -105,6 +109,14 @@ def _declare(lib):
     lib.eqd_dock_lddt_eval.restype = C.c_int
     lib.eqd_dock_lddt_eval.argtypes = ([C.c_int] + [C.c_void_p] * 10 + [C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
                                        [C.c_size_t, C.c_void_p])
+    lib.eqd_dock_depth_abi.restype = C.c_int
+    lib.eqd_dock_depth_workspace_bytes.restype = C.c_size_t
+    lib.eqd_dock_depth_workspace_bytes.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int]
+    lib.eqd_dock_depth_init.restype = C.c_int
+    lib.eqd_dock_depth_init.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.eqd_dock_depth_eval.restype = C.c_int
+    lib.eqd_dock_depth_eval.argtypes = ([C.c_int] + [C.c_void_p] * 13 + [C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 6 +
+                                        [C.c_size_t, C.c_void_p])
     lib.eqd_dock_emd_abi.restype = C.c_int
     lib.eqd_dock_emd_workspace_bytes.restype = C.c_size_t
     lib.eqd_dock_emd_workspace_bytes.argtypes = [C.c_int, C.c_void_p, C.c_int]
@@ -133,6 +145,8 @@ def _bind(path):
         raise _lib.EquidockHipError(f"{path}: dock SASA ABI {lib.eqd_dock_sasa_abi()} != {DOCK_SASA_ABI}")
     if lib.eqd_dock_lddt_abi() != DOCK_LDDT_ABI:
         raise _lib.EquidockHipError(f"{path}: dock lDDT ABI {lib.eqd_dock_lddt_abi()} != {DOCK_LDDT_ABI}")
+    if lib.eqd_dock_depth_abi() != DOCK_DEPTH_ABI:
+        raise _lib.EquidockHipError(f"{path}: dock depth ABI {lib.eqd_dock_depth_abi()} != {DOCK_DEPTH_ABI}")
     _dock, _dock_is_sim = lib, bool(lib.eqd_dock_is_simulator())
     return lib
 
@@ -925,8 +939,200 @@ def lddt_batch(lig_pred_list, lig_true_list, rec_true_list, lig_res_offsets=None
     return res
 
 
+# ---- batched residue depth ------------------------------------------------------------------------------------------
+DEPTH_KEYS = ('depth_ligand', 'depth_receptor', 'depth_complex', 'max_depth_ligand', 'max_depth_receptor',
+              'max_depth_complex', 'depth_gain_ligand', 'depth_gain_receptor', 'deepened_atoms_ligand',
+              'deepened_atoms_receptor', 'deepened_residues_ligand', 'deepened_residues_receptor', 'vertices_alone',
+              'vertices_complex', 'skipped_groups', 'flags')
+
+
+def depth_pruning_enabled():
+    """EQD_DOCK_DEPTH_PRUNE=0 turns the centre-and-reach bound on vertex groups of the depth pass off (same results but
+    for the count of skipped groups)."""
+    return os.environ.get('EQD_DOCK_DEPTH_PRUNE', '1') != '0'
+
+
+def _ca_rows(names, off, n_atoms, what):
+    """local row of the first atom named CA of every residue of a side, -1 where there is none (`names` None: all -1)"""
+    ca = np.full(len(off) - 1, -1, dtype=np.int64)
+    if names is None:
+        return ca
+    names = np.asarray(names, dtype=str).reshape(-1)
+    if len(names) != n_atoms:
+        raise ValueError(f"{what}: {len(names)} atom names for {n_atoms} atom rows")
+    rows = np.nonzero(np.char.strip(names) == 'CA')[0]
+    res = np.searchsorted(off, rows, side='right') - 1
+    ca[res[::-1]] = rows[::-1]                                  # (the first CA row of a residue wins)
+    return ca
+
+
+class DepthPlan:
+    """Workspace and tables of eqd_dock_depth_eval for one batch of complexes: the sphere table, the per-complex residue
+    offsets (local: [n_res + 1] into the complex's own rows), the rows of the residues' CA atoms (from `lig_names` /
+    `rec_names`, the atom names [n_atoms] of each complex as `atom_table` returns them; without them every CA row is -1)
+    and the radii ([n_atoms] float32, finite and > 0) go up in ONE copy, the workspace is created and initialised once
+    (init copies the tile table and waits for that copy); `eval` then only enqueues launches - it can be captured into a
+    hipGraph."""
+
+    def __init__(self, lig_res_offsets, rec_res_offsets, lig_radii, rec_radii, dev, n_points=96, lig_names=None,
+                 rec_names=None):
+        lib = load_dock_library()
+        n = len(lig_res_offsets)
+        if n == 0 or not (n == len(rec_res_offsets) == len(lig_radii) == len(rec_radii)):
+            raise ValueError(f"{n} ligand residue tables for {len(rec_res_offsets)} receptor residue tables, "
+                             f"{len(lig_radii)} ligand and {len(rec_radii)} receptor radius tables")
+        for nm, what in ((lig_names, 'ligand'), (rec_names, 'receptor')):
+            if nm is not None and len(nm) != n:
+                raise ValueError(f"{len(nm)} {what} name tables for {n} complexes")
+        lr = [_radii_table(r, f'complex {c}: ligand') for c, r in enumerate(lig_radii)]
+        rr = [_radii_table(r, f'complex {c}: receptor') for c, r in enumerate(rec_radii)]
+        lro = [_residue_table(o, len(r), f'complex {c}: ligand') for c, (o, r) in enumerate(zip(lig_res_offsets, lr))]
+        rro = [_residue_table(o, len(r), f'complex {c}: receptor') for c, (o, r) in enumerate(zip(rec_res_offsets, rr))]
+        lca = [_ca_rows(None if lig_names is None else lig_names[c], o, len(r), f'complex {c}: ligand')
+               for c, (o, r) in enumerate(zip(lro, lr))]
+        rca = [_ca_rows(None if rec_names is None else rec_names[c], o, len(r), f'complex {c}: receptor')
+               for c, (o, r) in enumerate(zip(rro, rr))]
+        self.n, self.dev, self.n_points = n, torch.device(dev), int(n_points)
+        _require_device(torch.empty(0, device=self.dev), 'depth inputs')
+        sphere = sphere_points(self.n_points)
+        self.lig_atom_off, self.rec_atom_off = _offsets([len(r) for r in lr]), _offsets([len(r) for r in rr])
+        self.lig_res_off, self.rec_res_off = _offsets([len(o) - 1 for o in lro]), _offsets([len(o) - 1 for o in rro])
+        self._off = tuple(a.ctypes.data_as(C.c_void_p) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off,
+                                                                  self.rec_res_off))
+        Al, Ar, Rl, Rr = (int(a[-1]) for a in (self.lig_atom_off, self.rec_atom_off, self.lig_res_off, self.rec_res_off))
+        self.sizes = (Al, Ar, Rl, Rr)
+        # one staging buffer, one upload: fp64 sphere table | int32 first rows of the ligand, of the receptor residues, CA
+        # rows of the ligand, of the receptor residues | fp32 radii of the ligand, of the receptor atoms
+        nb_s, nb_f = 24 * self.n_points, 4 * (2 * (Rl + Rr) + 2)
+        host = _staging(nb_s + nb_f + 4 * (Al + Ar), torch.uint8, self.dev)
+        h = host.numpy()
+        h[:nb_s].view(np.float64)[:] = sphere.reshape(-1)
+        ints = h[nb_s:nb_s + nb_f].view(np.int32)
+        ints[:Rl + 1] = np.concatenate([o[:-1] + int(a) for o, a in zip(lro, self.lig_atom_off)] + [[Al]])
+        ints[Rl + 1:Rl + Rr + 2] = np.concatenate([o[:-1] + int(a) for o, a in zip(rro, self.rec_atom_off)] + [[Ar]])
+        ints[Rl + Rr + 2:2 * Rl + Rr + 2] = np.concatenate([np.where(k >= 0, k + int(a), -1) for k, a in zip(lca, self.lig_atom_off)])
+        ints[2 * Rl + Rr + 2:] = np.concatenate([np.where(k >= 0, k + int(a), -1) for k, a in zip(rca, self.rec_atom_off)])
+        h[nb_s + nb_f:].view(np.float32)[:] = np.concatenate(lr + rr)
+        self.tables = host.to(self.dev, non_blocking=True)
+        self.sphere = self.tables[:nb_s].view(torch.float64).view(self.n_points, 3)
+        ints = self.tables[nb_s:nb_s + nb_f].view(torch.int32)
+        self.lig_first, self.rec_first = ints[:Rl + 1], ints[Rl + 1:Rl + Rr + 2]
+        self.lig_ca, self.rec_ca = ints[Rl + Rr + 2:2 * Rl + Rr + 2], ints[2 * Rl + Rr + 2:]
+        rad = self.tables[nb_s + nb_f:].view(torch.float32)
+        self.lig_radii, self.rec_radii = rad[:Al], rad[Al:]
+        self.wsb = lib.eqd_dock_depth_workspace_bytes(n, *self._off, self.n_points)
+        if self.wsb == 0:
+            check(2)
+        self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=self.dev)
+        with _lib.device_guard(self.dev):
+            check(lib.eqd_dock_depth_init(n, *self._off, self.n_points, _lib.ptr(self.ws), C.c_size_t(self.wsb),
+                                          _stream(self.dev)))
+
+    def outputs(self):
+        """Freshly allocated output buffers of one eval: (atom depths [A_l + A_r][4] fp64: s_alone, s_complex, depth_alone,
+        depth_complex; residue depths [R_l + R_r][4] fp64: mean alone, mean in complex, CA alone, CA in complex; rows
+        [C][16] fp64); the ligand's rows come first in the first two."""
+        Al, Ar, Rl, Rr = self.sizes
+        return (torch.empty(Al + Ar, 4, dtype=torch.float64, device=self.dev),
+                torch.empty(Rl + Rr, 4, dtype=torch.float64, device=self.dev),
+                torch.empty(self.n, DEPTH_COLS, dtype=torch.float64, device=self.dev))
+
+    def eval(self, lig, rec, depth, res_depth, rows, probe=1.4, prune=None):
+        """Enqueue the depth pass on the current stream: lig [A_l][3], rec [A_r][3] fp32 contiguous, the buffers of
+        `outputs()`.  No synchronisation, no allocation, no copy."""
+        Al, Ar, Rl, Rr = self.sizes
+        prune = depth_pruning_enabled() if prune is None else bool(prune)
+        with _lib.device_guard(self.dev):
+            check(_dock.eqd_dock_depth_eval(self.n, *self._off, _lib.ptr(lig), _lib.ptr(rec), _lib.ptr(self.lig_radii),
+                                            _lib.ptr(self.rec_radii), _lib.ptr(self.lig_first), _lib.ptr(self.rec_first),
+                                            _lib.ptr(self.lig_ca), _lib.ptr(self.rec_ca), _lib.ptr(self.sphere),
+                                            self.n_points, C.c_double(float(probe)), int(prune), _lib.ptr(depth[:Al]),
+                                            _lib.ptr(depth[Al:]), _lib.ptr(res_depth[:Rl]), _lib.ptr(res_depth[Rl:]),
+                                            _lib.ptr(rows), _lib.ptr(self.ws), C.c_size_t(self.wsb), _stream(self.dev)))
+        return rows
+
+
+def residue_depth_batch(lig_list, rec_list, lig_radii=None, rec_radii=None, lig_res_offsets=None, rec_res_offsets=None,
+                        lig_names=None, rec_names=None, probe=1.4, n_points=96, plan=None):
+    """Depth of every heavy atom and residue of C complexes below its protein's surface, alone and in complex, in one
+    device pass (eqd_dock_depth_*; the definitions are in include/equidock_dock.h): the distance to the nearest surface
+    vertex, a vertex being the van-der-Waals contact point of a Shrake-Rupley sphere point (`n_points` per atom, probe of
+    `probe` Angstrom) that stays exposed.  This is the contact patch of the solvent-excluded surface, not MSMS's surface:
+    re-entrant patches are not modelled.  It needs no native structure.  The lists hold device tensors [n_c, 3] of heavy
+    atoms; per complex (host arrays, as `atom_radii` / `atom_table` return them) the radii [n_c] (finite, > 0), the residue
+    offsets [n_res + 1] into its own rows of each side and optionally the atom names [n_c] (for the CA depth; without them
+    it is NaN) - or a `plan` (DepthPlan) that already holds them.  fp64 on the device from the fp32 rows; a complex's
+    results are bit-identical alone, in any batch and from run to run.
+
+    Returns a dict of device tensors: DEPTH_KEYS (float64 [C]: depth_ligand / depth_receptor - mean atom depth alone -,
+    depth_complex, max_depth_ligand / _receptor / _complex, depth_gain_ligand / _receptor - mean of depth in complex minus
+    depth alone -, deepened_atoms_ligand / _receptor, deepened_residues_ligand / _receptor, vertices_alone,
+    vertices_complex, skipped_groups, flags), `rows`, the raw [C][16] buffer, `lig_depth` / `rec_depth` (float64 [A][4]:
+    s_alone, s_complex, depth_alone, depth_complex), `lig_res_depth` / `rec_res_depth` (float64 [R][4]: mean alone, mean in
+    complex, CA alone, CA in complex) and `plan`.  One upload of the small tables (when no plan is given), one launch
+    sequence; apart from the tile-table copy of the workspace's init the call does not synchronise and downloads nothing."""
+    ligs, recs = list(lig_list), list(rec_list)
+    n = len(ligs)
+    if n != len(recs):
+        raise ValueError(f"{n} ligands for {len(recs)} receptors")
+    if n == 0:
+        raise ValueError("residue_depth_batch: no complexes")
+    ligs, recs = _meter_rows(ligs, 'ligand'), _meter_rows(recs, 'receptor')
+    dev = ligs[0].device
+    if plan is None:
+        if lig_radii is None or rec_radii is None or lig_res_offsets is None or rec_res_offsets is None:
+            raise ValueError("residue_depth_batch: radii and residue offsets of both sides (or a plan) are needed")
+        plan = DepthPlan(list(lig_res_offsets), list(rec_res_offsets), list(lig_radii), list(rec_radii), dev,
+                         n_points=n_points, lig_names=None if lig_names is None else list(lig_names),
+                         rec_names=None if rec_names is None else list(rec_names))
+    if plan.n != n:
+        raise ValueError(f"the plan holds {plan.n} complexes, the lists {n}")
+    for c in range(n):
+        nl, nr = int(plan.lig_atom_off[c + 1] - plan.lig_atom_off[c]), int(plan.rec_atom_off[c + 1] - plan.rec_atom_off[c])
+        if ligs[c].shape[0] != nl or recs[c].shape[0] != nr:
+            raise ValueError(f"complex {c}: {ligs[c].shape[0]} ligand and {recs[c].shape[0]} receptor rows for tables of "
+                             f"{nl} and {nr} atoms")
+    depth, res_depth, rows = plan.outputs()
+    plan.eval(torch.cat(ligs, 0), torch.cat(recs, 0), depth, res_depth, rows, probe=probe)
+    Al, Rl = plan.sizes[0], plan.sizes[2]
+    res = {k: rows[:, i] for i, k in enumerate(DEPTH_KEYS)}
+    res.update(rows=rows, lig_depth=depth[:Al], rec_depth=depth[Al:], lig_res_depth=res_depth[:Rl],
+               rec_res_depth=res_depth[Rl:], plan=plan)
+    return res
+
+
+def _average_ranks(v):
+    order = np.argsort(v, kind='stable')
+    s = v[order]
+    start = np.concatenate(([True], s[1:] != s[:-1]))
+    first = np.nonzero(start)[0]
+    last = np.concatenate((first[1:], [len(v)])) - 1
+    mean = 0.5 * (first + last) + 1.0                           # a run of ties takes the mean of its 1-based positions
+    ranks = np.empty(len(v), dtype=np.float64)
+    ranks[order] = mean[np.cumsum(start) - 1]
+    return ranks
+
+
+def spearman(a, b):
+    """Spearman's rank correlation of two equally long vectors (the statistic of scipy.stats.spearmanr): float64 on the
+    host, average ranks for ties, then Pearson's correlation of the ranks; NaN for fewer than two values or when one input
+    is constant."""
+    a = np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float64).reshape(-1)
+    b = np.asarray(b.detach().cpu() if torch.is_tensor(b) else b, dtype=np.float64).reshape(-1)
+    if len(a) != len(b):
+        raise ValueError(f"spearman: {len(a)} values for {len(b)}")
+    if len(a) < 2:
+        return float('nan')
+    ra, rb = _average_ranks(a), _average_ranks(b)
+    da, db = ra - ra.mean(), rb - rb.mean()
+    den = np.sqrt((da * da).sum() * (db * db).sum())
+    if not den > 0.0:
+        return float('nan')
+    return float((da * db).sum() / den)
+
+
 # ---- batched graph construction -------------------------------------------------------------------------------------
-GRAPH_KEYS = ('x', 'res_feat', 'mu_r_norm', 'src', 'dst', 'he')
+GRAPH_KEYS =('x', 'res_feat', 'mu_r_norm', 'src', 'dst', 'he')
 last_graph_stats = {}      # of the latest protein_graphs_batch call: proteins, residues, edges, pairs, pruned_pairs, pruning
 
 
@@ -1202,6 +1408,30 @@ def _chunk_surface(chunk, truths, first, final_lig, rec_atoms, probe, n_points, 
     return s['rows'].cpu().numpy()
 
 
+def _chunk_depth(chunk, first, final_lig, rec_atoms, probe, n_points, dev):
+    """The depth stage of dock_complexes for one chunk: the heavy-atom rows of the final ligands and of the receptors (the
+    rows `_chunk_surface` takes) taken on the device by an index built on the host, one residue_depth_batch, ONE download
+    of the [C][16] rows."""
+    lig_t, rec_t = [], []
+    for k, (lig_in, rec_in) in enumerate(chunk):
+        lig_t.append(atom_table(lig_in) + (atom_radii(lig_in),))
+        rec_t.append(atom_table(rec_in) + (atom_radii(rec_in),))
+        if len(lig_t[-1][4]) == 0 or len(rec_t[-1][4]) == 0:
+            raise ValueError(f"complex {first + k}: a side without a heavy atom")
+    n = len(chunk)
+    idx = [t[1] for t in lig_t + rec_t]
+    hidx = _staging(sum(len(a) for a in idx), torch.int64, dev)
+    hidx.numpy()[:] = np.concatenate(idx)
+    didx = hidx.to(dev, non_blocking=True)
+    ioff = np.concatenate([[0], np.cumsum([len(a) for a in idx])])
+    ligs = [final_lig[k].index_select(0, didx[ioff[k]:ioff[k + 1]]) for k in range(n)]
+    recs = [rec_atoms[k].index_select(0, didx[ioff[n + k]:ioff[n + k + 1]]) for k in range(n)]
+    d = residue_depth_batch(ligs, recs, [t[5] for t in lig_t], [t[5] for t in rec_t], [t[2] for t in lig_t],
+                            [t[2] for t in rec_t], lig_names=[t[4] for t in lig_t], rec_names=[t[4] for t in rec_t],
+                            probe=probe, n_points=n_points)
+    return d['rows'].cpu().numpy()
+
+
 def _sync(dev):
     if dev.type == 'cuda':
         torch.cuda.synchronize(dev)
@@ -1232,7 +1462,7 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                    max_neighbor=10, sigma=8.0, surface_ct=8.0, loss_stop=0.5, max_it=2000, check_every=50,
                    batched_graphs=True, ground_truth=None, interface_cutoff=8.0, quality=False,
                    quality_cutoffs=(5.0, 10.0, 3.0), surface=False, surface_probe=1.4, surface_points=96, lddt=False,
-                   lddt_radius=15.0):
+                   lddt_radius=15.0, depth=False, depth_probe=1.4, depth_points=96):
     """Dock a list of (ligand, receptor) complexes, each side a PDB path or a list of featurize.Residue (the ligand's
     file / residues in their input pose, the receptor's in the bound pose - the reference's `*_l_b.pdb` and
     `*_r_b_COMPLEX.pdb`).  Per chunk of `max_complexes_per_batch` complexes (all at once by default): graphs on the
@@ -1269,7 +1499,13 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
     (the rows and the heavy-atom-name check of `quality`; the model's receptor is the receptor given; inclusion radius
     `lddt_radius`, thresholds 0.5, 1, 2 and 4 Angstrom) and one more download, and the results gain `lddt`, `ilddt`
     (floats; ilddt NaN when no inter-chain atom pair of the native is closer than the radius), `lddt_pairs` and
-    `ilddt_pairs` (ints: the included ordered atom pairs); batch_seconds gains 'lddt'.  lddt=False changes nothing."""
+    `ilddt_pairs` (ints: the included ordered atom pairs); batch_seconds gains 'lddt'.  lddt=False changes nothing.
+
+    `depth` (needs no ground truth): each chunk ends with one residue_depth_batch over EVERY heavy atom of its final
+    ligands and receptors (the rows of `surface`; radii by atom_radii, probe `depth_probe`, `depth_points` sphere points)
+    and one more download, and the results gain `depth_gain_ligand`, `depth_gain_receptor` (floats, Angstrom: the mean
+    over the side's atoms of the depth in complex minus the depth alone), `deepened_atoms_ligand` / `_receptor` and
+    `deepened_residues_ligand` / `_receptor` (ints); batch_seconds gains 'depth'.  depth=False changes nothing."""
     complexes = list(complexes)
     if quality and ground_truth is None:
         raise ValueError("quality=True needs ground_truth")
@@ -1322,7 +1558,7 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
             t4 = time.perf_counter()
             times = {'graphs': t1 - t0, 'model': t2 - t1, 'rigid': t3 - t2, 'clashes': t4 - t3, 'total': t4 - t0,
                      'n_complexes': len(chunk)}
-            rows = qrows = srows = lrows = None
+            rows = qrows = srows = lrows = drows = None
             if ground_truth is not None:
                 final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
                 rows = _chunk_metrics(chunk, ground_truth[b0:b0 + len(chunk)], b0, final, rec_atoms, interface_cutoff, dev)
@@ -1344,6 +1580,12 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                                        rec_atoms, surface_probe, surface_points, dev)
                 te = time.perf_counter()           # (the download has synchronised)
                 times.update(surface=te - ts, total=te - t0)
+            if depth:
+                final = [cl[i]['positions'] if cl[i] is not None else docked[i] for i in range(len(chunk))]
+                td = time.perf_counter()           # (every earlier stage has synchronised)
+                drows = _chunk_depth(chunk, b0, final, rec_atoms, depth_probe, depth_points, dev)
+                tf = time.perf_counter()           # (the download has synchronised)
+                times.update(depth=tf - td, total=tf - t0)
             for i in range(len(chunk)):
                 results.append({'rotation': rots[i].detach().cpu().numpy(), 'translation': trs[i].detach().cpu().numpy().reshape(3),
                                 'ligand_atoms_docked': docked[i],
@@ -1370,8 +1612,76 @@ def dock_complexes(net, complexes, remove_clashes=True, max_complexes_per_batch=
                 if lrows is not None:
                     results[-1].update(lddt=float(lrows[i, 0]), ilddt=float(lrows[i, 1]), lddt_pairs=int(lrows[i, 4]),
                                        ilddt_pairs=int(lrows[i, 5]))
+                if drows is not None:
+                    d = drows[i]
+                    results[-1].update(depth_gain_ligand=float(d[6]), depth_gain_receptor=float(d[7]),
+                                       deepened_atoms_ligand=int(d[8]), deepened_atoms_receptor=int(d[9]),
+                                       deepened_residues_ligand=int(d[10]), deepened_residues_receptor=int(d[11]))
     finally:
         net.train(was_training)
+    return results
+
+
+# ---- the surface-feature analysis (src/surface_analysis.py) -----------------------------------------------------------
+def surface_feature_analysis(complexes, device, cutoff=30.0, max_neighbor=10, probe=1.4, n_points=96):
+    """The reference's src/surface_analysis.py for a list of (ligand, receptor) complexes, each side a PDB path (read with
+    featurize.read_pdb_residues) or a list of featurize.Residue: the Spearman correlation, over the graph nodes of each
+    side, between the residue's mean depth below its own protein's surface (alone) and -mu_r_norm[:, 4], the widest-scale
+    surface-aware node feature.  The graphs of the filtered residues come from ONE protein_graphs_batch, the depths from
+    ONE residue_depth_batch over every heavy atom of the UNFILTERED residue lists (tables by atom_table) - the surface is
+    the contact patch under the probe, not MSMS's, so the correlations are not the reference's digit for digit.  A graph
+    node is matched to its residue of atom_table by counting the residues of the list that have a heavy atom.
+
+    Returns one dict per complex: `spearman_ligand`, `spearman_receptor` (floats), `n_ligand`, `n_receptor` (graph nodes
+    matched), `depth_ligand`, `depth_receptor` and `feature_ligand`, `feature_receptor` (float64 numpy vectors, one entry
+    per graph node).  A side that cannot be matched - fewer than two residues pass the N / CA / C filter, a side of its
+    complex has no heavy atom, or the graph's node count differs - gives NaN and empty vectors; nothing is raised for
+    it (the reference skips such files)."""
+    dev = torch.device(device)
+    sides = []                                      # per side: (residues, filtered, rows of the filtered ones in atom_table)
+    for lig_in, rec_in in complexes:
+        for x in (lig_in, rec_in):
+            res = FZ.read_pdb_residues(x) if isinstance(x, (str, os.PathLike)) else list(x)
+            heavy = np.asarray([any(not _is_hydrogen(nm, el) for nm, el in
+                                    zip(r.atom_names, r.elements if len(r.elements) == len(r.atom_names) else [''] * len(r.atom_names)))
+                                for r in res], dtype=bool)
+            table_row = np.cumsum(heavy) - 1        # the residue's entry in atom_table(res), where it has one
+            keep = [i for i, r in enumerate(res) if len(r.atom('N')) == 1 and len(r.atom('CA')) == 1 and len(r.atom('C')) == 1]
+            sides.append((res, [res[i] for i in keep], table_row[keep] if keep else np.zeros(0, dtype=np.int64)))
+    n = len(sides) // 2
+    graphed = [k for k, s in enumerate(sides) if len(s[1]) >= 2]
+    graphs = dict(zip(graphed, protein_graphs_batch([(sides[k][1], FZ.alpha_carbon_array(sides[k][1])) for k in graphed], cutoff,
+                                                    max_neighbor, dev)))
+    tabs = [atom_table(s[0]) + (atom_radii(s[0]),) for s in sides]
+    batch = [c for c in range(n) if len(tabs[2 * c][0]) > 0 and len(tabs[2 * c + 1][0]) > 0]
+    res_depth = {}
+    if batch:
+        lt, rt = [tabs[2 * c] for c in batch], [tabs[2 * c + 1] for c in batch]
+        coords = np.concatenate([t[0] for t in lt + rt], 0)
+        h = _staging(coords.size, torch.float32, dev)
+        h.numpy()[:] = coords.reshape(-1)
+        d = h.to(dev, non_blocking=True).view(-1, 3)
+        off = np.concatenate([[0], np.cumsum([len(t[0]) for t in lt + rt])])
+        m = len(batch)
+        out = residue_depth_batch([d[off[k]:off[k + 1]] for k in range(m)], [d[off[m + k]:off[m + k + 1]] for k in range(m)],
+                                  [t[5] for t in lt], [t[5] for t in rt], [t[2] for t in lt], [t[2] for t in rt],
+                                  lig_names=[t[4] for t in lt], rec_names=[t[4] for t in rt], probe=probe, n_points=n_points)
+        both = torch.cat((out['lig_res_depth'][:, 0], out['rec_res_depth'][:, 0])).cpu().numpy()     # the one download
+        roff = np.concatenate([[0], np.cumsum([len(t[2]) - 1 for t in lt + rt])])
+        for k, c in enumerate(batch):
+            res_depth[2 * c] = both[roff[k]:roff[k + 1]]
+            res_depth[2 * c + 1] = both[roff[m + k]:roff[m + k + 1]]
+    results = []
+    for c in range(n):
+        r = {}
+        for k, tag in ((2 * c, 'ligand'), (2 * c + 1, 'receptor')):
+            depth, feat = np.zeros(0), np.zeros(0)
+            if k in graphs and k in res_depth and graphs[k]['host']['mu_r_norm'].shape[0] == len(sides[k][2]):
+                depth = np.ascontiguousarray(res_depth[k][sides[k][2]], dtype=np.float64)
+                feat = -np.asarray(graphs[k]['host']['mu_r_norm'][:, 4], dtype=np.float64)
+            r.update({f'spearman_{tag}': spearman(depth, feat), f'n_{tag}': len(depth), f'depth_{tag}': depth,
+                      f'feature_{tag}': feat})
+        results.append(r)
     return results
 
 
@@ -1409,6 +1719,9 @@ def main(argv=None):
     p.add_argument('--lddt', action='store_true',
                    help='lDDT and interface lDDT of every docked pose against its native from one batched device pass per '
                         'batch over every heavy atom (needs every <name>_l_b_COMPLEX.pdb)')
+    p.add_argument('--depth', action='store_true',
+                   help='residue depth of every docked pose from one batched device pass per batch over every heavy atom: how '
+                        'much deeper below the surface binding puts the atoms of each side (needs no ground truth)')
     a = p.parse_args(argv)
     try:
         names = sorted(os.path.basename(f)[:-len('_l_b.pdb')] for f in glob.glob(os.path.join(a.input_dir, '*_l_b.pdb')))
@@ -1439,9 +1752,9 @@ def main(argv=None):
                              device=dev, cutoff=float(ca.get('graph_cutoff', 30.0)),
                              max_neighbor=int(ca.get('graph_max_neighbor', 10)), max_it=a.max_it,
                              batched_graphs=not a.no_batched_graphs, ground_truth=truths, quality=a.dockq, surface=a.surface,
-                             lddt=a.lddt)
+                             lddt=a.lddt, depth=a.depth)
         suffix = '_EQUIDOCK_NO_CLASHES.pdb' if a.remove_clashes else '_EQUIDOCK.pdb'
-        crmsd, irmsd, dockq, bsa, bsa_native, ilddt = [], [], [], [], [], []
+        crmsd, irmsd, dockq, bsa, bsa_native, ilddt, gain = [], [], [], [], [], [], []
         for nm, (lig_path, rec_path), r in zip(names, complexes, res):
             out = os.path.join(a.out_dir, nm + '_l_b' + suffix)
             INF.write_pdb_coordinates(lig_path, r['ligand_atoms'], out)
@@ -1474,6 +1787,10 @@ def main(argv=None):
             if a.lddt:
                 ilddt.append(r['ilddt'])
                 line += f"  lDDT {r['lddt']:.4f}  ilDDT {r['ilddt']:.4f}"
+            if a.depth:
+                gain.append(r['depth_gain_ligand'])
+                line += (f"  depth gain {r['depth_gain_ligand']:.3f} / {r['depth_gain_receptor']:.3f}  deepened residues "
+                         f"{r['deepened_residues_ligand']} / {r['deepened_residues_receptor']}")
             print(line, flush=True)
         wall = time.perf_counter() - t0
         print(f"Mean runtime: {wall / len(res):.4f} s per complex ({len(res)} complexes, {wall:.3f} s)")
@@ -1496,6 +1813,8 @@ def main(argv=None):
             ok = il[~np.isnan(il)]                  # (undefined without an inter-chain atom pair under the radius)
             print("ilDDT median/mean/std: %.4f / %.4f / %.4f" % (_stats(ok) if ok.size else (float('nan'),) * 3) +
                   ("  undefined %d" % (il.size - ok.size) if ok.size < il.size else ""))
+        if gain:
+            print("depth gain median/mean/std: %.3f / %.3f / %.3f" % _stats(gain))
     except Exception as e:          # noqa: BLE001 - a command-line tool: report and exit non-zero
         print(f"error: {type(e).__name__}: {e}", file=sys.stderr)
         return 1

@@ -271,6 +271,83 @@ EQD_DOCK_API int eqd_dock_sasa_eval(int n_complex, const int32_t* lig_atom_off, 
                                     size_t ws_bytes, void* stream);
 
 /*
+ * Batched residue depth: for EVERY heavy atom of C complexes the distance to the nearest vertex of its protein's surface,
+ * alone and in complex, in one device pass - from which the mean and the CA depth of each residue (Chakravarty &
+ * Varadarajan 1999; the quantity of the reference's src/surface_analysis.py) and how deep binding buries the interface
+ * follow.  The surface is NOT the one of MSMS: a vertex is the van-der-Waals contact point, under the probe, of a
+ * Shrake-Rupley sphere point that stays exposed - the contact patch of the solvent-excluded surface.  Re-entrant patches are
+ * not modelled, so depths are not comparable digit for digit with Biopython's ResidueDepth; they are defined exactly, below.
+ * fp64 arithmetic from the fp32 inputs, without contraction, exactly as written; a complex's results are bit-identical
+ * alone, in any batch, at any position and from run to run.
+ *
+ * Layout and inputs: exactly those of eqd_dock_sasa_* (fp32 rows and radii, HOST int32 atom / residue offsets, device
+ * lig_res_first / rec_res_first, the caller's fp64 sphere table u_k with 1 <= n_points <= EQD_DOCK_SASA_MAX_POINTS, an fp64
+ * probe, finite and > 0), and
+ *   lig_res_ca [R_l], rec_res_ca [R_r]  int32: the global row of each residue's atom named CA (the first such row), or -1
+ * Definitions.
+ *   Exposure         point k of atom i is exposed alone / in complex by the rule of eqd_dock_sasa_*, unchanged: with
+ *                    R_i = (double)r_i + probe and q = x_i + R_i * u_k the point is buried by j != i when
+ *                    (dx * dx + dy * dy) + dz * dz < R_j * R_j, d = q - x_j; j ranges over the atom's own side (alone) or
+ *                    over both sides (in complex).
+ *   Surface vertex   of an exposed point: v_ik = x_i + (double)r_i * u_k per component, one multiply then one add.
+ *   Squared depth    s_alone(j): the minimum of (dx * dx + dy * dy) + dz * dz, d = x_j - v_ik, over the alone-exposed vertices
+ *                    of j's own side; s_complex(j): the same minimum over the complex-exposed vertices of both sides.  A
+ *                    minimum does not depend on the order of its terms.  A side or a complex without any vertex gives
+ *                    +inf and sets a flag bit.
+ *   Depth            depth = sqrt(s).
+ *   Deepened         an atom when s_complex > s_alone (compared on the squared values); a residue when at least one of its
+ *                    atoms is.  (depth_complex >= depth_alone is no invariant: the vertices of a clashing partner can lie
+ *                    inside an atom's sphere.)
+ *   Residue values   mean depth alone / in complex: the sum over the residue's atoms in row order, divided by the count; CA
+ *                    depth alone / in complex: the depth of row res_ca, NaN for -1.
+ *   Skipping         (prune != 0) a group of vertices - those of a tile of 64 consecutive rows of one side, or those of one
+ *                    atom - is passed over for an atom only by a bound that proves none of them beats the atom's running
+ *                    minimum: the distance to the group's centre minus the group's reach minus 1e-6, compared against the
+ *                    running minimum.  Results are identical with prune on or off on any input; only the count of skipped
+ *                    groups differs.
+ * Outputs.
+ *   lig_depth [A_l][4], rec_depth [A_r][4] fp64: s_alone, s_complex, depth_alone, depth_complex
+ *   lig_res_depth [R_l][4], rec_res_depth [R_r][4] fp64: mean alone, mean in complex, CA alone, CA in complex
+ *   rows [C][EQD_DOCK_DEPTH_COLS] fp64, all sums in row order, ligand before receptor:
+ *     0 / 1 mean atom depth of the ligand / receptor alone, 2 mean atom depth of all atoms in complex, 3 / 4 / 5 the largest
+ *     atom depth of the ligand alone / the receptor alone / all atoms in complex, 6 / 7 mean over the ligand's / receptor's
+ *     atoms of depth_complex - depth_alone, 8 / 9 deepened atoms of the ligand / receptor, 10 / 11 deepened residues of the
+ *     ligand / receptor, 12 / 13 vertices alone / in complex (eqd_dock_sasa_eval's columns 10 / 11 for the same inputs),
+ *     14 vertex groups skipped (0 with prune == 0; no other output depends on prune), 15 flags EQD_DOCK_DEPTH_FLAG_*
+ *     (columns 8-15 are integers stored as fp64)
+ * Sequence: workspace_bytes -> init (once per set of offsets and n_points) -> eval (any number of times).
+ */
+#define EQD_DOCK_DEPTH_ABI 1
+#define EQD_DOCK_DEPTH_COLS 16
+#define EQD_DOCK_DEPTH_FLAG_NO_LIGAND_VERTEX 1      /* the ligand alone has no exposed point: its s_alone are +inf */
+#define EQD_DOCK_DEPTH_FLAG_NO_RECEPTOR_VERTEX 2    /* the receptor alone has none */
+#define EQD_DOCK_DEPTH_FLAG_NO_COMPLEX_VERTEX 4     /* the complex has none: every s_complex is +inf */
+EQD_DOCK_API int eqd_dock_depth_abi(void);
+
+/* Workspace of a batch with these host offsets; 0 when they are invalid, do not fit 32-bit offsets or n_points is outside
+ * 1..EQD_DOCK_SASA_MAX_POINTS (eqd_dock_last_error says why). */
+EQD_DOCK_API size_t eqd_dock_depth_workspace_bytes(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                                   const int32_t* lig_res_off, const int32_t* rec_res_off, int n_points);
+
+/* Validates the offsets and writes the batch's tile table into the workspace (a host-to-device copy; this call waits for
+ * that copy). */
+EQD_DOCK_API int eqd_dock_depth_init(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                     const int32_t* lig_res_off, const int32_t* rec_res_off, int n_points, void* workspace,
+                                     size_t ws_bytes, void* stream);
+
+/* Enqueues the depth pass (five launches, whatever C is) on a workspace prepared by eqd_dock_depth_init with the same
+ * offsets and n_points.  No synchronisation, no allocation, no host-device copy: the call can be captured into a hipGraph.
+ * Invalid offsets, n_points outside 1..EQD_DOCK_SASA_MAX_POINTS, a probe that is not finite and > 0 or a workspace that is
+ * too small return an EQD_ERR_* code; nothing is launched then. */
+EQD_DOCK_API int eqd_dock_depth_eval(int n_complex, const int32_t* lig_atom_off, const int32_t* rec_atom_off,
+                                     const int32_t* lig_res_off, const int32_t* rec_res_off, const float* lig,
+                                     const float* rec, const float* lig_radius, const float* rec_radius,
+                                     const int32_t* lig_res_first, const int32_t* rec_res_first, const int32_t* lig_res_ca,
+                                     const int32_t* rec_res_ca, const double* sphere, int n_points, double probe, int prune,
+                                     double* lig_depth, double* rec_depth, double* lig_res_depth, double* rec_res_depth,
+                                     double* rows, void* workspace, size_t ws_bytes, void* stream);
+
+/*
  * Batched lDDT and interface lDDT (Mariani et al. 2013): the superposition-free, atom-level comparison of a model with its
  * native over EVERY heavy atom of C complexes in one device pass - per atom the distances to its native neighbours that
  * the model preserves, from which the lDDT of each residue, of each partner and of the complex follow, and the same
